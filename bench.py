@@ -18,13 +18,24 @@ Other workloads (the other single-GPU configs of BASELINE.json, same contract, s
   v8-sup  : the kernels of configs[4]: YOLOv8 (C2f / decoupled DFL head, width = depth = 1.0) supervised step with
             TaskAlignedAssigner + DFL loss, batch 32 per GPU (the reference has no runnable v8 SSOD step: SURVEY.md 8 a-14)
 
-Extra objects on the JSON line:
+A plain run (no --full) sets up, warms up, times the K steps, writes --dump-outputs if given, and prints the line: metric,
+value, unit, higher_is_better, dtype, ms_per_step and the configuration of the timed step.
+
+  --dump-outputs DIR  : after the timed steps, what the last timed step handed back -- its loss items, the BatchNorm running
+                        statistics and the student / EMA-teacher parameters its SGD / EMA updates wrote (a fixed, seeded sample of
+                        each arena) -- as DIR/<name>.npy, float32, rank 0.  The model then starts at the conditioned init and the last
+                        timed step starts from the state as built (DUMP_BN_WEIGHT below): same arguments, same results to rounding,
+                        so two builds can be compared output for output.
+  --full              : everything below as well (instrumented steps, extra runs and configurations; off by default).
+
+Extra objects on the JSON line with --full:
   roofline            : the dominant kernel (bf16 MFMA implicit-GEMM conv), algorithmic FLOPs per launch divided by its
                         HIP-event-measured average launch duration inside the timed region.
   kernel_ms_by_family : HIP-event time budget of ONE step by kernel family and stream (one extra instrumented step right
                         after the timed region, same overlap mode), so that the line itself shows where the step goes.
   cpu_baseline        : the plain-torch CPU port of the same step (oracle/) timed on the host cores, rank 0 at N = 1 only,
                         on a bounded sample;  parity_check: fp32-mode and bf16-mode HIP steps against that oracle step.
+  roofline_hbm, roofline_power, weak_scaling_point (N = 8), config.grad_allreduce, config.host_enqueue_ms_empty_queue.
 """
 import argparse
 import json
@@ -125,21 +136,110 @@ def load_cfg(wl, batch_size, extra=()):
 
 
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
+# --dump-outputs: what the last timed step computes is the same in every run, to rounding.  The step sums BatchNorm statistics and
+# weight-gradient splits with fp32 atomics, whose order changes the last bits, and two things would turn those bits into different results:
+#  * the default init (BatchNorm weights 1): this ~100-layer train-mode-BatchNorm network is chaotic there, the
+#    gradients of two runs part within one step -- with --dump-outputs every BatchNorm weight starts at DUMP_BN_WEIGHT instead (the
+#    conditioned init of tests/test_step_fullsize.py);
+#  * the training trajectory: from random weights, at the warm-up learning rates of ni = 2000 on the loss x batch of the reference,
+#    rounding-level differences grow from step to step -- with --dump-outputs the trainer state as built (weights, BatchNorm running
+#    statistics, optimizer momentum, both EMAs) is copied once and put back right before the LAST timed step, which is therefore one
+#    real training step (real learning rates, backward, SGD, EMA updates) from a state that is the same in every run.
+# A run without --dump-outputs times exactly the step it always did (default init, uninterrupted trajectory).
+DUMP_BN_WEIGHT = 0.3
 
 
-def build_trainer(device, rank, world, local_rank, per_rank, wl=None, dtype="bf16"):
+def _conditioned(trainer_cls):
+    """trainer_cls whose model is built with every BatchNorm weight at DUMP_BN_WEIGHT (before the arenas, optimizer and EMAs exist)"""
+    class DumpTrainer(trainer_cls):
+        def _model_class(self):
+            base = super()._model_class()
+
+            def make(cfg):
+                model = base(cfg)
+                with torch.no_grad():
+                    for m in model.modules():
+                        if isinstance(m, torch.nn.BatchNorm2d):
+                            m.weight.fill_(DUMP_BN_WEIGHT)
+                return model
+            return make
+    return DumpTrainer
+
+
+def build_trainer(device, rank, world, local_rank, per_rank, wl=None, dtype="bf16", conditioned=False):
+    """conditioned: every BatchNorm weight at DUMP_BN_WEIGHT (--dump-outputs)"""
     wl = wl or WORKLOADS["v5l-ssod"]
     torch.manual_seed(0)
     lr, rk = (local_rank if world > 1 else -1), (rank if world > 1 else -1)
     if os.environ.get("ET_DP_SINGLE_RANK", "0") == "1" and world == 1 and dist.is_initialized():
         lr, rk = local_rank, rank                        # single-GPU box: run the data-parallel code path over a 1-rank RCCL group
+    wrap = _conditioned if conditioned else (lambda c: c)
     if wl["kind"] == "ssod":
         from efficientteacher_amd.trainer import SSODTrainer
         cfg = load_cfg(wl, per_rank * world, ["SSOD.fixed_accumulate", True])
-        return cfg, SSODTrainer(cfg, device, None, lr, rk, world, nb=1000, amp_dtype=DTYPES[dtype])
+        return cfg, wrap(SSODTrainer)(cfg, device, None, lr, rk, world, nb=1000, amp_dtype=DTYPES[dtype])
     from efficientteacher_amd.trainer import Trainer
     cfg = load_cfg(wl, max(64, per_rank * world))        # accumulate = max(round(64 / batch), 1) = 1: optimizer every step
-    return cfg, Trainer(cfg, device, None, lr, rk, world, nb=1000, amp_dtype=DTYPES[dtype])
+    return cfg, wrap(Trainer)(cfg, device, None, lr, rk, world, nb=1000, amp_dtype=DTYPES[dtype])
+
+
+def _state_arenas(tr):
+    """the device tensors that carry the trainer's state from one step to the next"""
+    model = tr.model.module if hasattr(tr.model, "module") else tr.model
+    flats = [model.flat_state()] + [e.ema.flat_state() for e in (getattr(tr, "ema", None), getattr(tr, "semi_ema", None)) if e is not None]
+    tensors = [t for f in flats for t in (f.params, f.buffers)]
+    if getattr(getattr(tr, "optimizer", None), "momentum_buf", None) is not None:
+        tensors.append(tr.optimizer.momentum_buf)
+    return flats, tensors
+
+
+def snapshot_state(tr):
+    return [t.detach().clone() for t in _state_arenas(tr)[1]]
+
+
+def restore_state(tr, snap):
+    """put the state of snapshot_state() back, stream-ordered; the 16-bit weight copies follow the fp32 masters"""
+    flats, tensors = _state_arenas(tr)
+    with torch.no_grad():
+        for t, s in zip(tensors, snap):
+            t.copy_(s)
+        for f in flats:
+            f.sync_shadow()
+            f.mark_weights_changed()
+
+
+DUMP_PARAM_SAMPLE = 2 << 20      # elements per arena in --dump-outputs (8 MB in fp32; three arenas + the loss items < 64 MB)
+DUMP_TOLERANCE = 1e-3            # relative L2 per array between two runs of one build (measured: <= 1.9e-4 on YOLOv5l SSOD and v5s-sup)
+
+
+def dump_outputs(out_dir, items, tr):
+    """--dump-outputs: what the last timed step handed back, as <name>.npy (float32).  loss_<key>: the loss items
+    train_instance / train_step return; bn_running_stats: the student's BatchNorm running means and variances; student_params,
+    teacher_params: the fp32 parameter arenas of the student and of the EMA teacher.  An arena larger than DUMP_PARAM_SAMPLE is sampled
+    at that many fixed positions (seed 0, sorted).  The parameters are those the step's SGD and EMA updates wrote, so they carry the
+    backward pass.  Same arguments, same inputs and starting state (see DUMP_BN_WEIGHT): two runs of one build agree within DUMP_TOLERANCE
+    (relative L2 per array).  The optimizer's momentum arena (the raw bf16-mode gradients) is not written: it differs by ~3 % between
+    two runs of one build, the rounding noise of bf16 gradients through this network."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    if isinstance(items, dict):
+        loss = {f"loss_{k}": v for k, v in items.items()}
+    else:
+        loss = {"loss_items": items}
+    arrays = {k: torch.as_tensor(v).detach().float().cpu().numpy() for k, v in loss.items()}
+    model = tr.model.module if hasattr(tr.model, "module") else tr.model
+    arenas = [("student_params", model.flat_state().params), ("bn_running_stats", model.flat_state().buffers)]
+    if getattr(tr, "ema", None) is not None:
+        arenas.append(("teacher_params", tr.ema.ema.flat_state().params))
+    for name, p in arenas:
+        n = p.numel()
+        if n > DUMP_PARAM_SAMPLE:
+            idx = torch.randint(0, n, (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            p = p[idx.to(p.device)]
+        arrays[name] = p.detach().float().cpu().numpy()
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.astype(np.float32))
+    return sorted(arrays)
 
 
 # ---- CPU baseline + parity ---------------------------------------------------------------------------------------------
@@ -465,13 +565,14 @@ def _respawn(a):
 
 
 # ---- one measured configuration ----------------------------------------------------------------------------------------
-def measure(a, wl_name, per_rank, device, rank, world, dev_index, full=True):
-    """warm-up + timed region + (full=True) the instrumented extras for ONE per-rank batch size; returns a dict of results.
-    Collective: every rank calls this with the same arguments."""
+def measure(a, wl_name, per_rank, device, rank, world, dev_index, full=True, dump_dir=None):
+    """warm-up + timed region + (dump_dir) the outputs of the last timed step + (full=True) the instrumented extras for ONE
+    per-rank batch size; returns a dict of results.  Collective: every rank calls this with the same arguments."""
     from efficientteacher_amd import _lib, ops
     wl = WORKLOADS[wl_name]
     ssod = wl["kind"] == "ssod"
-    cfg, tr = build_trainer(device, rank, world, dev_index, per_rank, wl, a.dtype)
+    cfg, tr = build_trainer(device, rank, world, dev_index, per_rank, wl, a.dtype, conditioned=bool(dump_dir))
+    snap = snapshot_state(tr) if dump_dir else None      # the starting state of the last timed step (see DUMP_BN_WEIGHT)
     rng = np.random.default_rng(1234 + rank)
     S = cfg.Dataset.img_size
     Bl = Bu = per_rank
@@ -563,7 +664,10 @@ def measure(a, wl_name, per_rank, device, rank, world, dev_index, full=True):
         if ssod:
             tr.use_graph = graph_default and not (i in timed and full)   # HIP events cannot be recorded inside a replayed graph:
         if ddp is not None:                                              # the instrumented step(s) of the timed region run eagerly
-            ddp.timing = i in timed
+            ddp.timing = i in timed and full
+        if snap is not None and i == a.steps - 1:
+            restore_state(tr, snap)
+            snap = None
         items = step(a.warmup + i)
         if step_walls is not None:
             step_walls.append(time.perf_counter())
@@ -593,7 +697,9 @@ def measure(a, wl_name, per_rank, device, rank, world, dev_index, full=True):
                graph_probe=((getattr(tr._graph, "probe_ms", None), tr.eager_step_ms(), getattr(tr._graph, "slow_captures", 0))
                             if getattr(tr, "_graph", None) else None),
                graph_error=getattr(tr, "graph_error", None), graph_requested=bool(a.graph and ssod), graph_extra_warmup=n_extra,
-               n_timed=len(timed), timer=timer, S=S)
+               n_timed=len(timed) if full else 0, timer=timer, S=S)
+    if dump_dir and rank == 0:
+        res["dumped"] = dump_outputs(dump_dir, items, tr)
     if not full:
         del tr
         torch.cuda.empty_cache()
@@ -812,6 +918,10 @@ def main():
                     "BASELINE config of the workload (v5l-ssod: 32, and 16 at --gpus 8 = configs[3], global 128+128)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"], help="compute dtype of the timed step: bf16 (default performance "
                     "mode) or fp16 (the reference's autocast dtype, with the device-resident loss scaler; same MFMA rate)")
+    ap.add_argument("--full", action="store_true", help="also the instrumented extras: roofline / per-family time budget (extra "
+                    "instrumented steps), CPU baseline and parity check, the weak-scaling point at --gpus 8; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned "
+                    "(loss items, sampled student / teacher parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-teacher-alone", action="store_true", help="skip the teacher-forward-alone timing after the timed region (profiling "
                     "runs: its seven extra forwards would count into the per-step kernel totals)")
@@ -829,13 +939,17 @@ def main():
     ap.add_argument("--host-inputs", action="store_true", help="PCIe-inclusive variant: every step receives its three "
                     "uint8 image batches from pinned host memory (never the reported `value`; noted in DESIGN.md)")
     ap.add_argument("--dump-launches", default=None, help="write (kernel, flops, bytes, ms) of every timed conv launch of the "
-                    "instrumented step to this JSON file (tools/launch_table.py prints it)")
+                    "instrumented step to this JSON file (tools/launch_table.py prints it); implies --full")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); 'gloo' lets two "
                     "ranks share ONE GPU to exercise the N>1 code path where only a single GPU is available")
     ap.add_argument("--force-dp", action="store_true", help="--gpus 1 only: run the data-parallel code path (broadcasts, chunked "
                     "asynchronous AVG all-reduce from the gradient-ready hook, graph capture of the collectives) over a ONE-rank "
                     "RCCL group -- the way to execute that path on a single-GPU box")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_launches:
+        a.full = True           # the launch table comes from the instrumented step of a full run
     for kv in a.set:
         import ast
         import importlib
@@ -881,9 +995,9 @@ def main():
     per_rank = a.per_rank or (16 if (ssod and world == 8) else wl["per_rank"])
     if ssod and not a.no_graph and per_rank < 32 and a.backend == "nccl":
         a.graph = True          # small per-GPU batches: the ~16 ms of host enqueue are no longer small against the GPU step
-    res = measure(a, a.workload, per_rank, device, rank, world, dev_index, full=True)
+    res = measure(a, a.workload, per_rank, device, rank, world, dev_index, full=a.full, dump_dir=a.dump_outputs)
     weak = None
-    if ssod and world == 8 and per_rank != 32 and not a.no_weak_point and not a.per_rank:
+    if a.full and ssod and world == 8 and per_rank != 32 and not a.no_weak_point and not a.per_rank:
         keep_graph = a.graph
         a.graph = False
         weak = measure(a, a.workload, 32, device, rank, world, dev_index, full=False)
@@ -892,17 +1006,22 @@ def main():
     if rank == 0:
         cfg, dt, S = res["cfg"], res["dt"], res["S"]
         ips = res["imgs_per_step"]
-        try:                 # the roofline leg must never cost the throughput line
-            roof, conv_fl = roofline_of(res, a.dump_launches)
-        except Exception as e:
-            roof, conv_fl = dict(bound="mfma", kernel=None, achieved=None, peak=PEAK_BF16 / 1e12, unit="TFLOP/s", frac=None,
-                                 traffic=None, error=f"{type(e).__name__}: {e}"), None
+        roof, conv_fl = None, None
+        if a.full:
+            try:                 # the roofline leg must never cost the throughput line
+                roof, conv_fl = roofline_of(res, a.dump_launches)
+            except Exception as e:
+                roof, conv_fl = dict(bound="mfma", kernel=None, achieved=None, peak=PEAK_BF16 / 1e12, unit="TFLOP/s", frac=None,
+                                     traffic=None, error=f"{type(e).__name__}: {e}"), None
         if a.workload == "v5l-ssod":
             alg_flop = F_IMG * per_rank + 3 * F_IMG * (2 * per_rank)                     # the number BASELINE quotes
             da = bool(cfg.SSOD.with_da_loss)
             step_flop = alg_flop - (0.0 if da else 2 * F_NETD_IMG * (2 * per_rank))      # EXECUTED: no netD backward without the DA loss
         else:
-            alg_flop = step_flop = conv_fl if conv_fl else float("nan")      # measured: sum of 2*M*N*K over every conv launch of the step
+            # measured: sum of 2*M*N*K over every conv launch of the step (the instrumented step of --full; unknown in a plain run)
+            alg_flop = step_flop = conv_fl if conv_fl else (float("nan") if a.full else None)
+        tflop = lambda f: None if f is None else f / 1e12
+        step_flop_per_s = None if step_flop is None else step_flop / (dt / a.steps)
         if ssod:
             base_cfg = "BASELINE configs[2]" if (world == 1 and per_rank == 32) else \
                        ("BASELINE configs[3]: global 128 labeled + 128 unlabeled over 8 ranks" if (world == 8 and per_rank == 16) else
@@ -920,12 +1039,12 @@ def main():
             "replaced by U^16 / U^4 so that NMS and the pseudo-label loss do representative work)" if ssod else "; uniform uint8 images, synthetic COCO-80 targets)"),
             "config": {"workload": workload, "global_batch": world * ips, "img_size": S,
                        "parallelism": f"dp{world}", "optimizer_every_step": True,
-                       "algorithmic_tflop_per_step_per_gpu": alg_flop / 1e12,
-                       "executed_tflop_per_step_per_gpu": step_flop / 1e12,
+                       "algorithmic_tflop_per_step_per_gpu": tflop(alg_flop),
+                       "executed_tflop_per_step_per_gpu": tflop(step_flop),
                        "flop_note": "algorithmic = SURVEY.md 8(d) (teacher F + student 3F, netD included); executed = the same minus the netD "
                                     "backward, which SSOD.with_da_loss False never runs; step_tflops / frac_of_bf16_mfma_peak use EXECUTED",
-                       "step_tflops_per_gpu": step_flop / (dt / a.steps) / 1e12,
-                       "frac_of_bf16_mfma_peak": step_flop / (dt / a.steps) / PEAK_BF16, "loss_finite": res["loss_ok"], "loss_scale_after_the_timed_region": res.get("loss_scale"),
+                       "step_tflops_per_gpu": tflop(step_flop_per_s),
+                       "frac_of_bf16_mfma_peak": None if step_flop_per_s is None else step_flop_per_s / PEAK_BF16, "loss_finite": res["loss_ok"], "loss_scale_after_the_timed_region": res.get("loss_scale"),
                        "rccl_ranks": dist.get_world_size() if dist.is_initialized() else 1, "env_knobs": ops.env_knobs(), "module_overrides": list(a.set),
                        "rccl_env": rccl_env or None,
                        "grad_allreduce": (dict(bytes=int(sum(b for b, _ in t_ar[2])), arena_bytes=res["grad_bytes"],
@@ -951,11 +1070,18 @@ def main():
                        "inputs": "host uint8 (PCIe inclusive)" if a.host_inputs else
                                  ("resident in HBM (fp32, pre-divided by 255)" if a.float_inputs else
                                   "resident in HBM (uint8 NCHW as the loaders deliver; / 255 inside the timed step)")},
-            "roofline": roof,
-            "roofline_hbm": roofline_hbm(a.workload, per_rank, dt / a.steps),
-            "kernel_ms_by_family": res.get("families"),
         }
-        out["roofline_power"] = roofline_power(step_flop, (out["roofline_hbm"] or {}).get("traffic"), dt / a.steps)
+        if res.get("dumped"):
+            out["config"]["dump_outputs"] = dict(
+                arrays=res["dumped"], bn_weight_init=DUMP_BN_WEIGHT, tolerance_rel_l2=DUMP_TOLERANCE,
+                note="with --dump-outputs every BatchNorm weight starts at bn_weight_init and the trainer state as built is put back "
+                     "right before the last timed step, so that step (real learning rates, backward, SGD, EMAs) starts from the same "
+                     "state in every run")
+        if a.full:
+            out["roofline"] = roof
+            out["roofline_hbm"] = roofline_hbm(a.workload, per_rank, dt / a.steps)
+            out["kernel_ms_by_family"] = res.get("families")
+            out["roofline_power"] = roofline_power(step_flop, (out["roofline_hbm"] or {}).get("traffic"), dt / a.steps)
         if ssod and world == 8 and per_rank == 16:
             out["scaling_note"] = ("BASELINE configs[3]: the global batch equals that of 4 ranks at configs[2]'s per-GPU batch (strong "
                                    "scaling 4 -> 8); the per-GPU-work-fixed point of the same 8 ranks is `weak_scaling_point`")
@@ -964,7 +1090,7 @@ def main():
                                              value=world * weak["imgs_per_step"] * a.steps / weak["dt"], unit="images/s",
                                              ms_per_step=weak["dt"] / a.steps * 1e3, steps=a.steps, warmup=a.warmup, scaling="weak",
                                              global_batch=world * weak["imgs_per_step"])
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 res.clear()
                 torch.cuda.empty_cache()

@@ -27,7 +27,7 @@ def run_cell(gpus, per_rank, steps, warmup, graph, chunk_mb, channels, port, tim
     env.pop("ET_RCCL_CHANNELS", None)
     if channels:
         env["ET_RCCL_CHANNELS"] = str(channels)
-    args = ["--gpus", str(gpus), "--per-rank", str(per_rank), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline",
+    args = ["--gpus", str(gpus), "--per-rank", str(per_rank), "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline",
             "--no-weak-point", "--graph" if graph else "--no-graph"]
     if gpus == 1:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dp"] + args

@@ -1,6 +1,6 @@
 """Per-shape table of the conv launches of ONE instrumented step (HIP events per launch).
 
-  python bench.py --steps 12 --warmup 4 --no-cpu-baseline --dump-launches launches.json
+  python bench.py --steps 12 --warmup 4 --full --no-cpu-baseline --dump-launches launches.json
   python tools/launch_table.py launches.json
 
 Groups the launches by (kernel, op, shape), prints time, TFLOP/s and -- for the 256x256-tile kernels -- how full the last

@@ -14,10 +14,10 @@ t_new) run t_new; timeout 1500 python -m pytest tests/test_step_benchbatch.py te
 t_conv) run t_conv; timeout 1200 python -m pytest tests/test_conv.py tests/test_conv_fuzz.py tests/test_norm_spatial.py -x -q -m gpu > $OUT/pytest_conv.log 2>&1; tail -5 $OUT/pytest_conv.log ;;
 t_all) run t_all; timeout 2400 python -m pytest tests -x -q -m gpu -rs > $OUT/pytest_gpu.log 2>&1; tail -8 $OUT/pytest_gpu.log ;;
 smoke) run smoke; timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -3 $OUT/smoke.log ;;
-bench) run bench; timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; cut -c1-400 $OUT/bench.json; tail -3 $OUT/bench.err ;;
-bench_quick) run bench_quick; timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2> $OUT/bench_quick.err | tee $OUT/bench_quick.json | line quick ;;
+bench) run bench; timeout 900 python bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; cut -c1-400 $OUT/bench.json; tail -3 $OUT/bench.err ;;
+bench_quick) run bench_quick; timeout 900 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline 2> $OUT/bench_quick.err | tee $OUT/bench_quick.json | line quick ;;
 launches) run launches; timeout 900 python bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-teacher-alone --dump-launches $OUT/launches_one_step.json > $OUT/bench_launches.json 2> $OUT/launches.err; python tools/launch_table.py $OUT/launches_one_step.json > $OUT/launch_table.txt 2>&1; tail -16 $OUT/launch_table.txt ;;
-ab_env) run ab_env; for K in ${AB_ENV:-"X=0"}; do env $K timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | line "$K" | tee -a $OUT/ab_env.txt; done ;;
+ab_env) run ab_env; for K in ${AB_ENV:-"X=0"}; do env $K timeout 600 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | line "$K" | tee -a $OUT/ab_env.txt; done ;;
 mb_k1) run mb_k1; for K in ${MB_K1_ENV:-"X=0"}; do echo "--- $K" | tee -a $OUT/mb_k1.txt; env $K MB_REF=0 MB_K=1 MB_ROTATE=3 MB_B=${MB_B:-64} timeout 600 python tools/microbench.py conv 2>&1 | python -c "
 import sys, json, os
 B=int(os.environ.get('MB_B','64'))
