@@ -26,6 +26,10 @@ SIGNATURES = {
     "et_nms": (c_int, [P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, ctypes.c_uint64, ctypes.c_uint64, c_int,
                        c_float, c_int, P, P, P, P, P, c_size_t, P]),
     "et_nms_ssod": (c_int, [P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, P, P, P, P, P, c_size_t, P]),
+    "et_val_match": (c_int, [P, c_int, P, c_int, c_int, P, c_int, P, c_int, c_int, P, c_int, c_int, c_int, c_int64, c_int64,
+                             P, P, P, P, P, P]),
+    "et_val_ap_workspace_bytes": (c_int, [c_int, ctypes.POINTER(c_size_t)]),
+    "et_val_ap": (c_int, [P, P, P, c_int64, P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "et_detect_decode": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64,
                                  P, c_float, P, c_int64, c_int64, P]),
     "et_ema_update": (c_int, [P, P, c_int64, c_float, c_float, P]),
@@ -118,7 +122,7 @@ _emulated = False
 CALL_TIMER = None
 _NO_LAUNCH = frozenset(n for n in (
     "et_build_arch", "et_abi_version", "et_nms_ssod_workspace_bytes", "et_nms_workspace_bytes", "et_conv2d_stats_rows", "et_conv2d_stats_rows_for",
-    "et_conv2d_kernel_name", "et_env_knobs", "et_bn_reduce_rows", "et_ota_workspace_bytes", "et_tal_assign_workspace_bytes"))
+    "et_conv2d_kernel_name", "et_env_knobs", "et_bn_reduce_rows", "et_ota_workspace_bytes", "et_tal_assign_workspace_bytes", "et_val_ap_workspace_bytes"))
 
 
 class _TimedDll:

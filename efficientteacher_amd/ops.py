@@ -701,6 +701,51 @@ def score_log_append(dets, counts, conf_log, cls_log, log_count):
                                                _lib.stream(dets)), "et_score_log_append")
 
 
+def val_match(dets, counts, targets, shapes, net_hw, iouv, nc, correct, conf, cls, valid, nt, row_offset=0, single_cls=False):
+    """one validation batch of val.py:340-376 (csrc/metrics.hip): dets (B, max_det, >=6) fp32 + counts (B) int32 as et_nms leaves
+    them, targets (NT, 6) fp32 [img, cls, xywh normalised], shapes (B, 5) fp32 [gain, pad_x, pad_y, h0, w0], iouv (niou) fp32 --
+    all on the device -> rows row_offset .. row_offset + B*max_det of the arena tensors correct / cls / valid (int32) and conf
+    (fp32); nt (nc) int32 += labels per class.  Stream-ordered, no host synchronisation."""
+    B, max_det = dets.shape[0], dets.shape[1]
+    if dets.dtype != torch.float32 or dets.stride(2) != 1 or (B > 1 and dets.stride(0) != max_det * dets.stride(1)):
+        dets = dets.float().contiguous()
+    assert counts.dtype == torch.int32 and counts.numel() == B and counts.is_contiguous()
+    targets = targets.reshape(-1, 6)
+    if targets.dtype != torch.float32 or not targets.is_contiguous():
+        targets = targets.float().contiguous()
+    assert shapes.dtype == torch.float32 and shapes.shape == (B, 5) and shapes.is_contiguous()
+    assert iouv.dtype == torch.float32 and iouv.is_contiguous() and nt.dtype == torch.int32 and nt.numel() == nc
+    rows = conf.numel()
+    assert correct.dtype == cls.dtype == valid.dtype == torch.int32 and conf.dtype == torch.float32
+    assert correct.numel() == cls.numel() == valid.numel() == rows
+    NT = targets.shape[0]
+    _lib.check(_lib.load().et_val_match(_lib.ptr(dets), dets.stride(1), _lib.ptr(counts), B, max_det,
+                                        _lib.ptr(targets) if NT else None, NT, _lib.ptr(shapes), int(net_hw[0]), int(net_hw[1]),
+                                        _lib.ptr(iouv), iouv.numel(), int(bool(single_cls)), int(nc), int(row_offset), rows,
+                                        _lib.ptr(correct), _lib.ptr(conf), _lib.ptr(cls), _lib.ptr(valid), _lib.ptr(nt),
+                                        _lib.stream(conf)), "et_val_match")
+
+
+def val_ap(cls_sorted, correct_sorted, conf_sorted, nt, niou):
+    """ap_per_class + compute_ap (utils/metrics.py:22-126) over rows ordered by (class, conf descending), padding rows (class >= nc)
+    last -> ap (nc, niou), p, r, f1 (nc, 1000) fp64 on the device; rows of classes without labels or predictions are zero"""
+    import ctypes
+    nc, N, dev = nt.numel(), conf_sorted.numel(), nt.device
+    assert cls_sorted.dtype == correct_sorted.dtype == nt.dtype == torch.int32 and conf_sorted.dtype == torch.float32
+    assert cls_sorted.numel() == correct_sorted.numel() == N
+    assert cls_sorted.is_contiguous() and correct_sorted.is_contiguous() and conf_sorted.is_contiguous()
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t()
+    _lib.check(lib.et_val_ap_workspace_bytes(nc, ctypes.byref(nbytes)), "et_val_ap_workspace_bytes")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    ap = torch.empty((nc, niou), dtype=torch.float64, device=dev)
+    p, r, f1 = (torch.empty((nc, 1000), dtype=torch.float64, device=dev) for _ in range(3))
+    _lib.check(lib.et_val_ap(_lib.ptr(cls_sorted) if N else None, _lib.ptr(correct_sorted) if N else None,
+                             _lib.ptr(conf_sorted) if N else None, N, _lib.ptr(nt), nc, int(niou), _lib.ptr(ap), _lib.ptr(p),
+                             _lib.ptr(r), _lib.ptr(f1), _lib.ptr(ws), nbytes.value, _lib.stream(nt)), "et_val_ap")
+    return ap, p, r, f1
+
+
 class DeviceThresholds:
     """The per-class (low, high) pseudo-label thresholds of ComputeStudentMatchLoss as ONE persistent fp64 device tensor
     (2, nc) per loss object.  The trainer rewrites the host lists when LabelMatch adapts them (ssod_trainer.py:322-323);

@@ -118,6 +118,18 @@ class _HotPath:
     ET_COMPUTE_DTYPE = torch.bfloat16
     # hot_path_trainers(deterministic=True): bit-reproducible BatchNorm statistics in the 16-bit modes (Model.set_deterministic)
     ET_DETERMINISTIC = False
+    # hot_path_trainers(device_val=True): end-of-epoch validation through this package's val.run instead of the reference's
+    ET_DEVICE_VAL = False
+
+    def _et_val(self, val):
+        return DeviceVal(val) if (self.ET_DEVICE_VAL and val is not None and not isinstance(val, DeviceVal)) else val
+
+    # ---- trainer.py:445, :493 -----------------------------------------------------------------------------------
+    def after_epoch(self, callbacks, val):
+        return super().after_epoch(callbacks, self._et_val(val))
+
+    def after_train(self, callbacks, val):
+        return super().after_train(callbacks, self._et_val(val))
 
     def _et_model(self, cfg, device):
         import importlib
@@ -356,19 +368,49 @@ class _SsodHotPath(_HotPath):
     join_teacher_late = True
 
 
-def hot_path_trainers(ref_trainer=None, ref_ssod_trainer=None, compute_dtype=torch.bfloat16, deterministic=False):
+class DeviceVal:
+    """stands in for the reference's ``val`` module, which train.py hands to ``after_epoch(callbacks, val)`` / ``after_train``
+    (trainer.py:445,493; their ``val.run`` calls: trainer.py:453, ssod_trainer.py:339-383): the end-of-epoch validation goes through this package's ``val.run`` -- inference, NMS, matching and AP on the
+    device.  Calls that ask for what stays host code of the reference (plots, save_json, save_txt, keypoints: the end-of-training
+    run of trainer.py:502 / ssod_trainer.py:544 does) are handed to the reference's own ``val.run`` unchanged."""
+
+    def __init__(self, ref_val):
+        self.ref_val = ref_val
+
+    def __getattr__(self, name):                     # everything else of the module (process_batch, ...)
+        return getattr(self.ref_val, name)
+
+    def run(self, data, model=None, dataloader=None, conf_thres=0.001, iou_thres=0.6, single_cls=False, augment=False, verbose=False,
+            half=True, compute_loss=None, val_ssod=False, plots=True, save_txt=False, save_hybrid=False, save_json=False,
+            num_points=0, eval_num=-1, names=None, **kw):
+        if model is None or dataloader is None or plots or save_txt or save_hybrid or save_json or num_points:
+            return self.ref_val.run(data, model=model, dataloader=dataloader, conf_thres=conf_thres, iou_thres=iou_thres,
+                                    single_cls=single_cls, augment=augment, verbose=verbose, half=half, compute_loss=compute_loss,
+                                    val_ssod=val_ssod, plots=plots, save_txt=save_txt, save_hybrid=save_hybrid, save_json=save_json,
+                                    num_points=num_points, eval_num=eval_num, names=names or {}, **kw)
+        from .. import val as et_val
+        half = half and next(model.parameters()).device.type != "cpu"            # val.py:189
+        return et_val.run(model, dataloader, conf_thres=conf_thres, iou_thres=iou_thres, half=half, single_cls=single_cls,
+                          augment=augment, compute_loss=compute_loss, val_ssod=val_ssod, nc=int(data["nc"]),
+                          names=names or data.get("names"), eval_num=eval_num, verbose=verbose)
+
+
+def hot_path_trainers(ref_trainer=None, ref_ssod_trainer=None, compute_dtype=torch.bfloat16, deterministic=False, device_val=False):
     """(Trainer, SSODTrainer): subclasses of the reference's trainers -- taken from the tree this is called in
     (``trainer.trainer.Trainer`` / ``trainer.ssod_trainer.SSODTrainer``) unless passed explicitly.
     compute_dtype: torch.bfloat16 (default: no loss scaling), torch.float16 (the reference's autocast dtype; ``self.scaler`` is then
     the device-resident GradScaler the reference's ``update_optimizer`` drives unchanged) or torch.float32 (parity mode).
-    deterministic: BatchNorm statistics of the 16-bit modes on the reproducible partial-row path (FlatState(deterministic=True))."""
+    deterministic: BatchNorm statistics of the 16-bit modes on the reproducible partial-row path (FlatState(deterministic=True)).
+    device_val: off by default (validation stays the reference's val.run); True routes the trainers' end-of-epoch ``val.run`` calls
+    through this package's device-resident ``val.run`` (``DeviceVal`` wraps the ``val`` module train.py passes in)."""
     if compute_dtype not in (torch.bfloat16, torch.float16, torch.float32):
         raise ValueError(f"compute_dtype {compute_dtype}")
     if ref_trainer is None or ref_ssod_trainer is None:
         from trainer.ssod_trainer import SSODTrainer as ref_ssod_trainer       # noqa: N813  (the user's tree)
         from trainer.trainer import Trainer as ref_trainer                     # noqa: N813
     hot = type("Trainer", (_HotPath, ref_trainer), {"__doc__": "reference Trainer with the MI355X hot path", "ET_COMPUTE_DTYPE": compute_dtype,
-                                                      "ET_DETERMINISTIC": bool(deterministic)})
+                                                      "ET_DETERMINISTIC": bool(deterministic), "ET_DEVICE_VAL": bool(device_val)})
     ssod = type("SSODTrainer", (_SsodHotPath, ref_ssod_trainer), {"__doc__": "reference SSODTrainer with the MI355X hot path",
-                                                                   "ET_COMPUTE_DTYPE": compute_dtype, "ET_DETERMINISTIC": bool(deterministic)})
+                                                                   "ET_COMPUTE_DTYPE": compute_dtype, "ET_DETERMINISTIC": bool(deterministic),
+                                                                   "ET_DEVICE_VAL": bool(device_val)})
     return hot, ssod

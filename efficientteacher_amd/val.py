@@ -1,24 +1,42 @@
-"""Per-batch inference path of the reference's validation loop (reference val.py:277-338):
+"""Validation on the device (reference val.py:149-465).
+
+Inference half, ``infer_batch`` (val.py:277-338):
 
     img uint8 -> (half | float) / 255 -> model(img) in eval mode (BatchNorm folded into the conv epilogues)
               -> non_max_suppression(out, conf_thres=0.001, iou_thres=0.6, multi_label=True, agnostic=single_cls)
 
-``infer_batch`` is that sequence on the MI355X kernels: the uint8 batch is normalised inside the input pack kernel, the
-EMA / student detector runs its folded-BN inference convs (bf16 when ``half``: the reference's fp16 switch maps to this
-package's bf16 compute mode), the decoded (B, A, 5+nc) tensor goes through et_nms (multi-label candidates, exact
-max_nms cut, class-offset NMS) and comes back as the reference's ``list[Tensor(n, 6)]``.  The mAP bookkeeping around it
-(val.py:339-420: ConfusionMatrix, ap_per_class, COCO json) is host code of the reference and stays there.
+the uint8 batch is normalised inside the input pack kernel, the EMA / student detector runs its folded-BN inference convs
+(bf16 when ``half``: the reference's fp16 switch maps to this package's bf16 compute mode), the decoded (B, A, 5+nc) tensor
+goes through et_nms (multi-label candidates, exact max_nms cut, class-offset NMS) and comes back as the reference's
+``list[Tensor(n, 6)]`` or, with ``padded=True``, as the device tensors ``(dets (B, max_det, 6), counts (B))`` et_nms wrote.
+
+Metric half, ``DetectionMetrics`` (val.py:339-403 + utils/metrics.py:16-126): ``update`` is one et_val_match launch per batch
+-- scale_coords, box_iou and process_batch for every image of the batch, results appended to a device arena at fixed row
+positions, no device->host transfer and no synchronisation -- and ``compute`` is one stable sort, one et_val_ap launch and one
+copy of a few KB to the host: P, R, AP per class and threshold, F1, the per-class F1-optimal confidence thresholds
+(``cls_thr``, which SSOD validation hands back to the trainer) and ``fitness``.
+
+``run`` is the reference's ``val.run`` over the two for a model and a loader that already exist (its ``training`` branch).
+Its ConfusionMatrix, plots, save_txt / save_json / pycocotools legs and the keypoint (num_points) variants are host code of the
+reference and stay there.
 """
 import torch
 
-from .utils.general import non_max_suppression
+import time
+
+import numpy as np
+
+from . import ops
+from .utils.general import nms_padded, non_max_suppression
 
 
 @torch.no_grad()
 def infer_batch(model, img, conf_thres=0.001, iou_thres=0.6, half=True, augment=False, single_cls=False, multi_label=True,
-                max_det=300, labels=()):
+                max_det=300, labels=(), padded=False):
     """One batch of val.run: returns (detections list[Tensor(n,6)] [x1,y1,x2,y2,conf,cls], train_out) -- train_out are the raw
-    head outputs the reference feeds to compute_loss (val.py:312-314)."""
+    head outputs the reference feeds to compute_loss (val.py:312-314).  padded=True: the detections stay the device tensors
+    (dets (B, max_det, 6) zero padded, counts (B,) int32) of et_nms, nothing is unpacked and the host is not synchronised --
+    the form ``DetectionMetrics.update`` takes."""
     if labels:
         raise NotImplementedError("save_hybrid autolabelling (labels=lb) stays on the reference's host path")
     was_training = model.training
@@ -38,7 +56,207 @@ def infer_batch(model, img, conf_thres=0.001, iou_thres=0.6, half=True, augment=
             out, train_out = out[0], out[1]
             break
         out = out[0]
-    dets = non_max_suppression(out, conf_thres, iou_thres, multi_label=multi_label, agnostic=single_cls, max_det=max_det)
+    if padded:
+        dets = nms_padded(out, conf_thres, iou_thres, agnostic=single_cls, multi_label=multi_label, max_det=max_det)[:2]
+    else:
+        dets = non_max_suppression(out, conf_thres, iou_thres, multi_label=multi_label, agnostic=single_cls, max_det=max_det)
     if was_training:
         model.train()
     return dets, train_out
+
+
+def fitness(x):
+    """utils/metrics.py:16-19: rows [P, R, mAP@.5, mAP@.5:.95, ...] -> 0.1 * mAP@.5 + 0.9 * mAP@.5:.95"""
+    w = [0.0, 0.0, 0.1, 0.9]
+    return (np.atleast_2d(np.asarray(x, dtype=np.float64))[:, :4] * w).sum(1)
+
+
+class DetectionResults:
+    """what ``ap_per_class`` returns (p, r, ap, f1, ap_class, cls_thr: utils/metrics.py:98) and what val.run derives from it
+    (val.py:401-403, :459-461): ap50, mp, mr, map50, map, nt, maps."""
+
+    def __init__(self, nc, niou):
+        self.p = self.r = self.f1 = np.zeros(0)
+        self.ap = np.zeros((0, niou))
+        self.ap50 = np.zeros(0)
+        self.ap_class = np.zeros(0, dtype=np.int32)
+        self.cls_thr = []
+        self.f1_index = 0
+        self.mp = self.mr = self.map50 = self.map = 0.0
+        self.nt = np.zeros(nc, dtype=np.int64)
+        self.maps = np.zeros(nc)
+
+    def fitness(self):
+        return float(fitness(np.array([[self.mp, self.mr, self.map50, self.map]]))[0])
+
+
+def shape_rows(shapes, net_hw):
+    """the loader's ``shapes`` (val.py:344,356: shapes[si] = ((h0, w0), ((gain_h, gain_w), (pad_x, pad_y))), or ((h0, w0), None) for
+    scale_coords to work the letterbox out itself, utils/general.py:704-706) -> (B, 5) fp32 rows [gain, pad_x, pad_y, h0, w0]"""
+    rows = []
+    for s in shapes:
+        (h0, w0), rp = s[0], (s[1] if len(s) > 1 else None)
+        if rp is None:
+            gain = min(net_hw[0] / h0, net_hw[1] / w0)
+            pad = (net_hw[1] - w0 * gain) / 2, (net_hw[0] - h0 * gain) / 2
+        else:
+            gain, pad = rp[0][0], rp[1]
+        rows.append([gain, pad[0], pad[1], h0, w0])
+    return torch.tensor(rows, dtype=torch.float32).reshape(-1, 5)
+
+
+class DetectionMetrics:
+    """Device-resident P / R / mAP accumulator (see the module docstring).
+
+    Order rules the reference leaves to unstable sorts: a detection with two class-matching labels of exactly equal IoU takes the
+    lower label index; detections of equal confidence are ranked in arena order (image, then NMS rank)."""
+
+    def __init__(self, nc, iouv=None, max_det=300, device=None):
+        self.nc, self.max_det = int(nc), int(max_det)
+        self.device = torch.device(device if device is not None else "cuda")
+        iouv = torch.linspace(0.5, 0.95, 10) if iouv is None else torch.as_tensor(iouv)          # val.py:244
+        self.iouv = iouv.detach().to("cpu", torch.float32).contiguous().to(self.device)
+        self.niou = self.iouv.numel()
+        assert 1 <= self.niou <= 16 and 1 <= self.max_det <= 1024
+        self.reset()
+
+    def reset(self):
+        self._rows = 0
+        self._arena = None
+        self.nt = torch.zeros(self.nc, dtype=torch.int32, device=self.device)
+        self.seen = 0
+
+    def _reserve(self, rows):
+        cap = 0 if self._arena is None else self._arena[0].numel()
+        if rows <= cap and self._arena is not None:
+            return
+        cap = max(rows, 2 * cap, 64 * self.max_det)
+        new = [torch.empty(cap, dtype=dt, device=self.device) for dt in (torch.int32, torch.float32, torch.int32, torch.int32)]
+        if self._arena is not None:
+            for a, b in zip(new, self._arena):
+                a[:self._rows].copy_(b[:self._rows])                 # device to device, stream ordered
+        self._arena = new
+
+    def update(self, dets, counts, targets, shapes, net_hw, single_cls=False):
+        """one batch: dets (B, max_det, >=6) + counts (B) from ``infer_batch(padded=True)``, targets (NT, 6) [img, cls, xywh
+        normalised] on the device, shapes: (B, 5) fp32 device rows [gain, pad_x, pad_y, h0, w0] or the loader's list
+        (``shape_rows``), net_hw: (height, width) of the network input."""
+        B = dets.shape[0]
+        assert dets.shape[1] == self.max_det, (dets.shape, self.max_det)
+        if not torch.is_tensor(shapes):
+            shapes = shape_rows(shapes, net_hw)
+            if self.device.type == "cuda":
+                shapes = shapes.pin_memory()
+        shapes = shapes.to(self.device, torch.float32, non_blocking=True).contiguous()
+        self._reserve(self._rows + B * self.max_det)
+        correct, conf, cls, valid = self._arena
+        ops.val_match(dets, counts, targets, shapes, net_hw, self.iouv, self.nc, correct, conf, cls, valid, self.nt,
+                      row_offset=self._rows, single_cls=single_cls)
+        self._rows += B * self.max_det
+        self.seen += B
+
+    def rows(self):
+        """the arena so far: correct (bit i = true positive at iouv[i]), conf, cls, valid -- device tensors, one row per
+        (image, NMS slot)"""
+        if self._arena is None:
+            z = torch.zeros(0, dtype=torch.int32, device=self.device)
+            return z, z.float(), z, z
+        return tuple(a[:self._rows] for a in self._arena)
+
+    def sorted_rows(self):
+        """the rows ordered by (class, conf descending, arena row): one stable sort of a packed 64-bit key"""
+        correct, conf, cls, valid = self.rows()
+        kc = torch.where((valid > 0) & (cls >= 0) & (cls < self.nc), cls, torch.full_like(cls, self.nc)).to(torch.int64)
+        key = (kc << 32) | ((~conf.view(torch.int32)).to(torch.int64) & 0xFFFFFFFF)   # conf >= 0: fp32 bits are monotone
+        order = torch.sort(key, stable=True).indices
+        return kc[order].to(torch.int32), correct[order].contiguous(), conf[order].contiguous()
+
+    def curves(self):
+        """ap (nc, niou), p, r, f1 (nc, 1000) fp64 on the device, indexed by class (utils/metrics.py:46-74)"""
+        cls_s, correct_s, conf_s = self.sorted_rows()
+        return ops.val_ap(cls_s, correct_s, conf_s, self.nt, self.niou)
+
+    def compute(self):
+        nc, niou = self.nc, self.niou
+        ap, p, r, f1 = self.curves()
+        correct = self.rows()[0]
+        # utils/metrics.py:83 f1.mean(0).argmax(): the rows of classes without labels are zero, so the sum over all classes has
+        # the same arg-max as the mean over the classes that have labels
+        i = f1.sum(0).argmax()
+        pack = torch.cat((ap.reshape(-1), p[:, i], r[:, i], f1[:, i], f1.argmax(1).double(), self.nt.double(),
+                          i.double().reshape(1), (correct != 0).any().double().reshape(1)))
+        h = pack.cpu().numpy()                                        # the one transfer
+        res = DetectionResults(nc, niou)
+        o = nc * niou
+        res.nt = h[o + 4 * nc:o + 5 * nc].astype(np.int64)
+        res.maps = np.zeros(nc)
+        if h[-1] == 0.0:                                              # val.py:399: nothing correct at any threshold -> zeros
+            return res
+        cl = np.nonzero(res.nt > 0)[0]                                # np.unique(target_cls), :41
+        px = np.linspace(0, 1, 1000)
+        res.ap_class = cl.astype(np.int32)
+        res.ap = h[:o].reshape(nc, niou)[cl]
+        res.p, res.r, res.f1 = h[o:o + nc][cl], h[o + nc:o + 2 * nc][cl], h[o + 2 * nc:o + 3 * nc][cl]
+        res.cls_thr = [px[int(k)] for k in h[o + 3 * nc:o + 4 * nc][cl]]
+        res.f1_index = int(h[-2])
+        res.ap50, apm = res.ap[:, 0], res.ap.mean(1)                  # val.py:401-402
+        res.mp, res.mr, res.map50, res.map = res.p.mean(), res.r.mean(), res.ap50.mean(), apm.mean()
+        res.maps = np.zeros(nc) + res.map                             # val.py:459-461
+        res.maps[cl] = apm
+        return res
+
+    def fitness(self):
+        return self.compute().fitness()
+
+
+@torch.no_grad()
+def run(model, dataloader, *, conf_thres=0.001, iou_thres=0.6, half=True, single_cls=False, augment=False, compute_loss=None,
+        val_ssod=False, nc=80, names=None, eval_num=-1, verbose=False, max_det=300, save_txt=False, save_json=False,
+        save_hybrid=False, plots=False, num_points=0):
+    """The reference's val.run (val.py:149-465) for a model and a loader that exist (its ``training`` branch):
+    returns ((mp, mr, map50, map, *loss), maps, t) and, with val_ssod, cls_thr as a fourth element; prints its table.
+    The three loss entries are zeros as in the reference, whose compute_loss call is unreachable (val.py:307 is always true);
+    ``compute_loss`` is accepted for call compatibility.  t = (pre-process, inference + NMS + matching, 0) ms per image: the stages
+    are not separated by device synchronisations here."""
+    for flag, what in ((save_txt, "save_txt (val.py:379)"), (save_json, "save_json / pycocotools (val.py:381, :428-452)"),
+                       (save_hybrid, "save_hybrid autolabelling (val.py:330)"), (plots, "plots / ConfusionMatrix (val.py:372, :386, :423)"),
+                       (num_points, "num_points keypoint validation (val.py:332, :357-364)")):
+        if flag:
+            raise NotImplementedError(f"{what} stays on the reference's host path")
+    device = next(model.parameters()).device
+    nc = 1 if single_cls else int(nc)                                # val.py:243
+    if names is None:
+        inner = model.module if hasattr(model, "module") else model
+        names = getattr(inner, "names", None) or {}
+    if isinstance(names, (list, tuple)):
+        names = dict(enumerate(names))
+    metrics = DetectionMetrics(nc, max_det=max_det, device=device)
+    s = ('%20s' + '%11s' * 6) % ('Class', 'Images', 'Labels', 'P', 'R', 'mAP@.5', 'mAP@.5:.95')
+    dt = [0.0, 0.0, 0.0]
+    nbatches = 0
+    for batch_i, (img, targets, paths, shapes) in enumerate(dataloader):
+        if batch_i == eval_num:                                      # val.py:277
+            break
+        t1 = time.perf_counter()
+        img = img.to(device, non_blocking=True)
+        targets = targets.to(device, non_blocking=True)
+        t2 = time.perf_counter()
+        (dets, counts), _ = infer_batch(model, img, conf_thres, iou_thres, half=half, augment=augment, single_cls=single_cls,
+                                        max_det=max_det, padded=True)
+        metrics.update(dets, counts, targets, shapes, img.shape[2:], single_cls=single_cls)
+        dt[0] += t2 - t1
+        dt[1] += time.perf_counter() - t2
+        nbatches += 1
+    t2 = time.perf_counter()
+    res = metrics.compute()
+    dt[1] += time.perf_counter() - t2
+    seen = metrics.seen
+    pf = '%20s' + '%11i' * 2 + '%11.3g' * 4
+    print(s)
+    print(pf % ('all', seen, res.nt.sum(), res.mp, res.mr, res.map50, res.map))
+    if verbose and nc > 1:                                           # val.py:412
+        for i, c in enumerate(res.ap_class):
+            print(pf % (names.get(int(c), str(int(c))), seen, res.nt[c], res.p[i], res.r[i], res.ap50[i], res.ap[i].mean()))
+    t = tuple(x / max(seen, 1) * 1E3 for x in dt)
+    out = (res.mp, res.mr, res.map50, res.map, 0.0, 0.0, 0.0), res.maps, t
+    return out + (res.cls_thr,) if val_ssod else out

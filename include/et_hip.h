@@ -31,7 +31,7 @@ enum { ET_F32 = 0, ET_BF16 = 1, ET_F16 = 2 };   /* ET_F16 (r05): IEEE half stora
  * for ("gfx950") and the ABI version.  ET_ABI_VERSION changes whenever an entry point is added or a signature / workspace
  * contract changes; a binding must refuse a library whose et_abi_version() differs from the header it was written against
  * (efficientteacher_amd/_lib.py does): a stale libet_hip.so would otherwise read e.g. a new int argument as the stream. */
-#define ET_ABI_VERSION 6
+#define ET_ABI_VERSION 7
 const char* et_build_arch(void);
 int et_abi_version(void);
 
@@ -60,6 +60,43 @@ int et_nms(const float* pred, int B, int A, int no, float conf_thres, float iou_
            int multi_label, uint64_t class_mask_lo, uint64_t class_mask_hi, int max_nms, float max_wh,
            int max_det, float* dets, int* counts, int64_t* keep, int* n_candidates, void* workspace,
            size_t ws_bytes, et_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Detection metrics (csrc/metrics.hip): the mAP bookkeeping of the validation loop, on the device.
+ *
+ * et_val_match replaces val.py:340-376 for one batch -- labels to pixels (:328) and xywh2xyxy (:367), scale_coords +
+ * clip_coords of both sets (utils/general.py:702-773), box_iou (utils/metrics.py:252-274) and process_batch
+ * (val.py:123-145) -- and the target-class bincount of :403.
+ *   dets    (B, max_det, det_row_stride >= 6) fp32 rows [x1,y1,x2,y2,conf,cls,..] + counts (B) int32, as et_nms writes them
+ *           (letterboxed-image pixels)
+ *   targets (NT, 6) fp32 rows [img, cls, x, y, w, h], xywh normalised to the network input as the dataloader gives them
+ *   shapes  (B, 5) fp32 rows [gain, pad_x, pad_y, h0, w0]: the loader's shapes[si] = ((h0, w0), ((gain, .), (pad_x, pad_y)))
+ *   iouv    (niou <= 16) fp32 DEVICE thresholds; single_cls: every detection counts as class 0 (val.py:353-354)
+ *   out, at arena row  row_offset + si * max_det + j  (fixed positions, nothing compacted, arena_rows = arena capacity):
+ *           correct int32 bit i = detection is a true positive at iouv[i]; conf fp32; cls int32 (-1 on padding rows);
+ *           valid int32 (j < counts[si]);   nt (nc) int32 += number of labels per class (integer atomics)
+ * Arithmetic is fp32 in the reference's operation order; the division by gain is a true division, as the reference's
+ * CPU-tensor path (where the golden is made) performs it.
+ * Tie rule: a detection with two class-matching labels of exactly equal IoU takes the one with the LOWER label index
+ * (target row order); the reference leaves this to an unstable sort (val.py:140).  Between two detections that chose the
+ * same label the lower detection index wins, as in the reference (its re-sort at val.py:142 is commented out).
+ * Limits: max_det <= 1024; no limit on labels.  B == 0 is a no-op. */
+int et_val_match(const float* dets, int det_row_stride, const int* counts, int B, int max_det, const float* targets, int NT,
+                 const float* shapes, int net_h, int net_w, const float* iouv, int niou, int single_cls, int nc,
+                 int64_t row_offset, int64_t arena_rows, int* correct, float* conf, int* cls, int* valid, int* nt,
+                 et_stream_t stream);
+
+/* et_val_ap replaces utils/metrics.py:22-126 (ap_per_class + compute_ap, without the plots) once per evaluation.
+ *   cls / correct / conf (N): the arena rows ALREADY ordered by (class ascending, conf descending); padding rows carry a
+ *           class >= nc and sort last.  Equal confidences inside a class keep the caller's order (the reference's
+ *           np.argsort(-conf) at :37 is unstable there).
+ *   nt (nc) int32 labels per class
+ *   out: ap (nc, niou), p / r / f1 (nc, 1000) fp64 -- rows of classes without labels or without predictions are zero
+ *        (:52-53); the caller selects the classes with labels (np.unique(target_cls), :41).
+ * Deterministic: integer counts, fp64 in numpy's operation order, no floating-point atomics. */
+int et_val_ap_workspace_bytes(int nc, size_t* bytes /*host out*/);
+int et_val_ap(const int* cls, const int* correct, const float* conf, int64_t N, const int* nt, int nc, int niou, double* ap,
+              double* p, double* r, double* f1, void* workspace, size_t ws_bytes, et_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Detect head inference decode.  Replaces models/head/yolov5_head.py:68-78 (+ _make_grid_old
