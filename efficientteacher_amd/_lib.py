@@ -54,6 +54,9 @@ SIGNATURES = {
     "et_weight_transpose": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "et_conv2d_kernel_name": (c_int, [c_int] * 13 + [c_char_p, c_int]),
     "et_env_knobs": (c_int, [c_char_p, c_int]),
+    "et_conv2d_stem_u8_fwd": (c_int, [P, P, c_int, c_float, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, c_int, P, P]),
+    "et_conv2d_stem_u8_wgrad": (c_int, [P, P, c_int, c_float, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "et_conv2d_stem_kernel_name": (c_int, [c_int] * 12 + [c_char_p, c_int]),
     "et_colsum": (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
     "et_bn_reduce_rows": (c_int, [c_int, c_int, c_int]),
     "et_bn_finalize": (c_int, [P, c_int, c_int, c_double, P, P, c_float, c_float, P, P, P, P, P, P, P, P]),
@@ -122,7 +125,7 @@ _emulated = False
 CALL_TIMER = None
 _NO_LAUNCH = frozenset(n for n in (
     "et_build_arch", "et_abi_version", "et_nms_ssod_workspace_bytes", "et_nms_workspace_bytes", "et_conv2d_stats_rows", "et_conv2d_stats_rows_for",
-    "et_conv2d_kernel_name", "et_env_knobs", "et_bn_reduce_rows", "et_ota_workspace_bytes", "et_tal_assign_workspace_bytes", "et_val_ap_workspace_bytes"))
+    "et_conv2d_kernel_name", "et_conv2d_stem_kernel_name", "et_env_knobs", "et_bn_reduce_rows", "et_ota_workspace_bytes", "et_tal_assign_workspace_bytes", "et_val_ap_workspace_bytes"))
 
 
 class _TimedDll:

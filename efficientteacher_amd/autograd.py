@@ -194,13 +194,19 @@ class ConvBnActFn(Function):
     train mode, plus the Bottleneck shortcut (common.py:544)."""
 
     @staticmethod
-    def forward(ctx, x, residual, wparam, cs, bs, act, nbt, dst=None, bn_in=None, bn_out=None, acc=None):
+    def forward(ctx, x, residual, wparam, cs, bs, act, nbt, dst=None, bn_in=None, bn_out=None, acc=None, u8=None):
         # wparam (the nn.Parameter) only ties the op into the autograd graph; its gradient is written
         # by the wgrad kernel directly into the flat arena, so backward returns None for it.
         # bn_in: BnBwdSums of the block that produced x, passed ONLY when this conv is x's sole consumer (the caller knows
         # the graph): this layer's dgrad then does that block's BatchNorm-backward reduce pass in its epilogue.
         # bn_out: a one-element list that receives this block's BnBwdSums for the (sole) consumer of z.
         # acc: the GradFork of x when x has a second consumer (see GradFork): this layer's dgrad adds into the parked gradient.
+        # The stem on the loaders' uint8 images: x is an ops.U8Images (the forward reads the planes) and / or u8 is one (the weight
+        # gradient reads them; x is then its packed tensor or the U8Images itself).  The node keeps REFERENCES to the uint8 tensors and
+        # the normalisation scale, no packed copy: THE CALLER MUST NOT OVERWRITE THE IMAGES BEFORE BACKWARD HAS FINISHED (the weight
+        # gradient reads them at the end of backward, on the weight-gradient stream; ops.WgradQueue.join() orders everything behind it).
+        ctx.u8 = u8
+        ctx.x_u8 = x if isinstance(x, ops.U8Images) else None
         ctx.w_needs_grad = wparam.requires_grad
         ctx.bn_in = bn_in if (bn_in is not None and cs.stride == 1 and residual is None) else None
         ctx.acc = acc
@@ -217,7 +223,7 @@ class ConvBnActFn(Function):
         if bn_out is not None and residual is None:
             ctx.bn_mine = _bn_sums(y, scale, shift, act, bs)
             bn_out.append(ctx.bn_mine)
-        ctx.save_for_backward(x, y, scale, shift, mean, invstd)
+        ctx.save_for_backward(None if ctx.x_u8 is not None else x, y, scale, shift, mean, invstd)
         return z
 
     @staticmethod
@@ -226,8 +232,11 @@ class ConvBnActFn(Function):
         cs, bs = ctx.cs, ctx.bs
         dz = _dense_or_slice(dz)
         dy = _bn_train_bwd(dz, y, bs, scale, shift, mean, invstd, ctx.act, sums=ctx.bn_mine)
-        if ctx.w_needs_grad:
-            _wgrad(x, dy, cs)
+        if ctx.w_needs_grad and ctx.u8 is not None:
+            hook = GRAD_READY_HOOK
+            ops.WGRAD_QUEUE.submit_stem_u8(ctx.u8, dy, cs.gw, on_done=(lambda: hook(cs)) if hook is not None else None)
+        elif ctx.w_needs_grad:
+            _wgrad(x if ctx.x_u8 is None else ctx.x_u8.packed(), dy, cs)      # (uint8 forward, packed weight gradient: the A/B arm ET_STEM_U8=1)
         dx = None
         if ctx.x_needs_grad:
             wT = cs.transposed()
@@ -237,7 +246,7 @@ class ConvBnActFn(Function):
                 ctx.acc.merged = True
             else:
                 dx = ops.conv2d_dgrad(dy, wT, (x.shape[1], x.shape[2]), cs.stride, cs.pad, bn=_fuse_into(cs, ctx.bn_in, x))
-        return dx, (dz if ctx.has_res else None), None, None, None, None, None, None, None, None, None
+        return dx, (dz if ctx.has_res else None), None, None, None, None, None, None, None, None, None, None
 
 
 class BottleneckFn(Function):

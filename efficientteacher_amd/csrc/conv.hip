@@ -1860,6 +1860,7 @@ __global__ __launch_bounds__(64 * WM * WN, WGS) void conv1x1_stream_flat_kernel(
 #define STEM_PSLOTS (7 * 256)           // 12 * 132 = 1584 slots, rounded up to whole staging instructions
 #define STEM_WPITCH 37
 #define STEM_WSLOTS (10 * 256)          // 64 * 37 = 2368 slots, rounded up
+#define STEM_MAX_SEGS 4
 
 struct StemArgs {
     const uint16_t* x; const uint16_t* w; uint16_t* y; const uint16_t* zero;
@@ -1868,15 +1869,42 @@ struct StemArgs {
     const float* scale; const float* bias; int act;
     float* stats; int stat_rows;        // [stat_rows][2][Cout] or null
     int stats_ld;                       // != 0: sharded accumulator [ET_BN_SHARDS][2][stats_ld] (Epilogue::stats_ld)
+    // the uint8 form (conv_stem_u8_kernel): the image is NOT the packed tensor x but up to four runs of uint8 NCHW images (3 planes each);
+    // image n belongs to the last segment whose first image seg_b[s] <= n (unused segments: seg_b = INT_MAX); value = byte / norm
+    const uint8_t* seg[STEM_MAX_SEGS]; int seg_b[STEM_MAX_SEGS]; float norm;
 };
 
-template <typename T, int ACT>
-__global__ __launch_bounds__(256, 2) void conv_stem_kernel(StemArgs a) {            // T: the 16-bit format behind StemArgs' raw pointers
+// image n -> its uint8 planes (wave-uniform: scalar selects over the kernel arguments)
+template <typename A> __device__ __forceinline__ const uint8_t* stem_u8_image(const A& a, int n) {
+    const uint8_t* p = a.seg[0];
+    int b = 0;
+#pragma unroll
+    for (int s = 1; s < STEM_MAX_SEGS; ++s)
+        if (n >= a.seg_b[s]) { p = a.seg[s]; b = a.seg_b[s]; }
+    return p + (size_t)(n - b) * 3 * a.IH * a.IW;
+}
+// lut[v] = T(v / norm): EXACTLY pack_input4_bf16_kernel's expression (spatial.hip: IEEE division, then the pack's rounding), so a pixel
+// staged through the table carries the bits the packed tensor would
+template <typename T> __device__ __forceinline__ void stem_u8_fill_lut(uint16_t* lut, int tid, float norm) {
+    lut[tid] = (uint16_t)(et_lp<T>::pack((float)((unsigned)tid & 0xffu) / norm, 0.f) & 0xffffu);
+}
+
+// U8 = false: the patch is staged by LDS-DMA from the packed image (a.x).  U8 = true: from the uint8 planes -- a thread fetches
+// whole aligned pixel QUADS (one dword per plane; the patch's 132 columns start 2 pixels into the first of 34 quads, IW % 4 == 0: a
+// quad is inside or outside the image as a whole) into registers while the previous tile's MFMAs run, and turns them into the packed
+// pixel layout (r, g, b, five zeros: one 16-byte LDS write per pixel) through the table at the head of its tile.  Everything behind
+// the patch -- operand offsets, MFMA order, epilogue -- is the same code, so the result is bit-identical to pack + conv_stem_kernel.
+#define STEM_QPR 34                     // pixel quads per patch row: columns -4 .. 131 relative to the first output column's 2*ox
+#define STEM_NQ (STEM_PH * STEM_QPR)    // 408 quads: 2 per thread
+template <typename T, int ACT, bool U8>
+__device__ __forceinline__ void conv_stem_body(const StemArgs& a) {            // T: the 16-bit format behind StemArgs' raw pointers
     __shared__ __attribute__((aligned(16))) u32x4 wl[STEM_WSLOTS];
     __shared__ __attribute__((aligned(16))) u32x4 pl[STEM_PSLOTS];
+    __shared__ uint16_t lut[U8 ? 256 : 2];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
+    if constexpr (U8) stem_u8_fill_lut<T>(lut, tid, a.norm);
 
     // ---- weights -> LDS once (pitch 37; channels >= Cout and the pad slot read the zero page)
 #pragma unroll
@@ -1930,13 +1958,62 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(StemArgs a) {        
             et_glds16(src, pl + i * 256 + wave * 64);
         }
     };
-    if ((int)blockIdx.x < a.ntiles) stage_patch(blockIdx.x);
+    // ---- uint8 form: this thread's two quads (patch row, quad column), their bytes of the tile in flight, and whether they are inside
+    int q_row[2], q_col[2];
+    unsigned q_px[2][3];
+    bool q_in[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int q = i * 256 + tid;
+        q_row[i] = q < STEM_NQ ? q / STEM_QPR : -100000;
+        q_col[i] = q % STEM_QPR;
+        q_in[i] = false;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) q_px[i][c] = 0u;
+    }
+    auto load_u8 = [&](int tile) {
+        const int tc = tile % a.tcn, t2 = tile / a.tcn;
+        const int tr = t2 % a.trn, n = t2 / a.trn;
+        const int iy0 = 2 * tr * STEM_TR - 2, ix0 = 2 * tc * STEM_TC - 4;
+        const uint8_t* const img = stem_u8_image(a, n);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int iy = iy0 + q_row[i], ix = ix0 + 4 * q_col[i];
+            q_in[i] = (unsigned)iy < (unsigned)a.IH && (unsigned)ix < (unsigned)a.IW;
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                q_px[i][c] = q_in[i] ? *(const unsigned*)(img + ((size_t)c * a.IH + iy) * a.IW + ix) : 0u;
+        }
+    };
+    auto write_patch_u8 = [&]() {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int pc = 4 * q_col[i] - 2 + j;
+                if (q_row[i] >= 0 && (unsigned)pc < (unsigned)STEM_PITCH) {
+                    const unsigned r = lut[(q_px[i][0] >> (8 * j)) & 0xffu], g = lut[(q_px[i][1] >> (8 * j)) & 0xffu];
+                    const unsigned b = lut[(q_px[i][2] >> (8 * j)) & 0xffu];
+                    pl[q_row[i] * STEM_PITCH + pc] = q_in[i] ? mk4(r | (g << 16), b, 0u, 0u) : mk4(0u, 0u, 0u, 0u);
+                }
+            }
+    };
+    if constexpr (U8) {
+        __syncthreads();                 // the table
+        if ((int)blockIdx.x < a.ntiles) load_u8(blockIdx.x);
+    } else {
+        if ((int)blockIdx.x < a.ntiles) stage_patch(blockIdx.x);
+    }
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
         const int tc = tile % a.tcn, t2 = tile / a.tcn;
         const int tr = t2 % a.trn, n = t2 / a.trn;
         const int oy0 = tr * STEM_TR, ox0 = tc * STEM_TC;
+        if constexpr (U8) write_patch_u8();       // every wave left the previous patch at the barrier behind its MFMAs
         et_wait_vmem();
         __syncthreads();
+        if constexpr (U8) {                       // the next tile's bytes travel while this tile's MFMAs and stores run
+            if (tile + (int)gridDim.x < a.ntiles) load_u8(tile + gridDim.x);
+        }
         // ---- 18 k-steps (two taps of one kernel row each): 2 channel blocks x 2 pixel blocks of 32x32x16 MFMAs
         f32x16 acc[2][2];
 #pragma unroll
@@ -1960,7 +2037,9 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(StemArgs a) {        
         }
         // every wave is done with the patch: the next tile's patch streams in behind this tile's epilogue
         __syncthreads();
-        if (tile + (int)gridDim.x < a.ntiles) stage_patch(tile + gridDim.x);
+        if constexpr (!U8) {
+            if (tile + (int)gridDim.x < a.ntiles) stage_patch(tile + gridDim.x);
+        }
         // ---- epilogue straight from registers: lane = pixel (l31 of block pb), register r = channel 8*(r>>2) + 4*hi + (r&3).
         // The two lanes of a pixel (hi = 0 / 1) each hold 4 of every 8 consecutive channels: they trade quads so that each
         // ends up with 8 whole channel octets -- 8 stores of 16 bytes per lane instead of 16 of 8 (the store tail of a
@@ -2037,6 +2116,10 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(StemArgs a) {        
         }
     }
 }
+template <typename T, int ACT>
+__global__ __launch_bounds__(256, 2) void conv_stem_kernel(StemArgs a) { conv_stem_body<T, ACT, false>(a); }
+template <typename T, int ACT>
+__global__ __launch_bounds__(256, 2) void conv_stem_u8_kernel(StemArgs a) { conv_stem_body<T, ACT, true>(a); }
 
 static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static int device_cus() {
@@ -2501,6 +2584,197 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_wgrad_tr_kernel(WgradGroup 
                 }
             }
     }
+}
+
+// ---- weight gradient of the stem (6x6 stride 2 pad 2) from dY and the uint8 image planes ------------------------------------------
+// The generic kernels run this layer on the packed image: GEMM-N = 36 taps x 8 channels = 288 columns of which 108 are real, and the
+// packed tensor is gathered once per tap.  Here the image never exists in packed form.  One (persistent) workgroup owns 4 x 64 output
+// pixels at a time, the forward's tile:
+//   * dY (256 pixels x 64 channels) arrives by LDS-DMA in its natural [pixel][channel] order, double buffered, and is read as the
+//     K(=pixel)-contiguous MFMA A operand with ds_read_b64_tr_b16, exactly as conv_wgrad_tr_kernel does;
+//   * the input patch (12 x 136 pixels) is built ONCE per tile from the uint8 planes through the forward's table (stem_u8_fill_lut: the
+//     same bits as the packed tensor), 8 bytes per pixel: r, g, b, 0.  The same transposing read then delivers the B operand straight
+//     from it: of a 16-lane group, lane 4j + t fetches the 8 bytes of the input pixel that tap t meets at output pixel j, and lane
+//     4t + c receives channel c of tap t for the four pixels.  GEMM-N = 36 taps x 4 channels = 144 (five 32-column blocks, half of
+//     the last one idle); every tap reads the patch at a constant offset -- nothing is staged per tap;
+//   * wave w reduces over output row w of the tile into a full 64 x 160 accumulator set that lives for the whole grid-stride loop; the
+//     four sets meet in LDS at the end and ONE wave adds the real columns (channel < 3, tap < 36) into dW [cout][ky][kx][8] with fp32
+//     atomics: one addition per workgroup and address, the pad slots are never touched.
+// HBM traffic: dY once plus 1.5 x the image bytes (row halo), against the packed path's nine-fold gather of a 16-byte pixel.
+#define SWG_PITCH 136                   // patch columns: 34 quads, column 0 = input column 2 * ox0 - 4
+#define SWG_DYV (256 * 8)               // dY tile in 16-byte slots
+struct StemWgradArgs {
+    const uint8_t* seg[STEM_MAX_SEGS]; int seg_b[STEM_MAX_SEGS]; float norm;
+    const uint16_t* dy; const uint16_t* zero; float* dw;
+    int N, IH, IW, OH, OW, ldy, Cout;
+    int trn, tcn, ntiles;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256, 2) void conv_stem_u8_wgrad_kernel(StemWgradArgs a) {
+    __shared__ __attribute__((aligned(16))) u32x4 dyl[2 * SWG_DYV];                   // 64 KB; the cross-wave reduction reuses it
+    __shared__ __attribute__((aligned(16))) u32x4 xl[STEM_PH * SWG_PITCH / 2];        // 8 bytes per pixel
+    __shared__ uint16_t lut[256];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, hi = lane >> 5;
+    stem_u8_fill_lut<T>(lut, tid, a.norm);
+
+    // ---- staging roles (constant over tiles)
+    int q_row[2], q_col[2];
+    unsigned q_px[2][3];
+    bool q_in[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int q = i * 256 + tid;
+        q_row[i] = q < STEM_NQ ? q / STEM_QPR : -100000;
+        q_col[i] = q % STEM_QPR;
+        q_in[i] = false;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) q_px[i][c] = 0u;
+    }
+    auto load_u8 = [&](int tile) {
+        const int tc = tile % a.tcn, t2 = tile / a.tcn;
+        const int tr = t2 % a.trn, n = t2 / a.trn;
+        const int iy0 = 2 * tr * STEM_TR - 2, ix0 = 2 * tc * STEM_TC - 4;
+        const uint8_t* const img = stem_u8_image(a, n);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int iy = iy0 + q_row[i], ix = ix0 + 4 * q_col[i];
+            q_in[i] = (unsigned)iy < (unsigned)a.IH && (unsigned)ix < (unsigned)a.IW;
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                q_px[i][c] = q_in[i] ? *(const unsigned*)(img + ((size_t)c * a.IH + iy) * a.IW + ix) : 0u;
+        }
+    };
+    auto write_patch = [&]() {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            if (q_row[i] < 0) continue;
+            unsigned w[8];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned r = lut[(q_px[i][0] >> (8 * j)) & 0xffu], g = lut[(q_px[i][1] >> (8 * j)) & 0xffu];
+                const unsigned b = lut[(q_px[i][2] >> (8 * j)) & 0xffu];
+                w[2 * j] = q_in[i] ? (r | (g << 16)) : 0u;
+                w[2 * j + 1] = q_in[i] ? b : 0u;
+            }
+            u32x4* const d = xl + (q_row[i] * SWG_PITCH + 4 * q_col[i]) / 2;
+            d[0] = mk4(w[0], w[1], w[2], w[3]);
+            d[1] = mk4(w[4], w[5], w[6], w[7]);
+        }
+    };
+    // dY slot i * 256 + tid: pixel slot >> 3 of the tile (row-major 4 x 64), physical 16-byte slot & 7 = channel group ^ swizzle
+    auto stage_dy = [&](int tile, int buf) {
+        const int tc = tile % a.tcn, t2 = tile / a.tcn;
+        const int tr = t2 % a.trn, n = t2 / a.trn;
+        const int oy0 = tr * STEM_TR, ox0 = tc * STEM_TC;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int slot = i * 256 + tid, p = slot >> 3;
+            const int co = ((slot & 7) ^ tr_swz<8>(p)) * 8;
+            const int oy = oy0 + (p >> 6), ox = ox0 + (p & 63);
+            const bool ok = oy < a.OH && ox < a.OW && co < a.Cout;
+            const uint16_t* src = ok ? a.dy + ((((size_t)n * a.OH + oy) * a.OW + ox) * a.ldy + co) : a.zero;
+            et_glds16(src, dyl + buf * SWG_DYV + i * 256 + wave * 64);
+        }
+    };
+
+    // ---- fragment addressing.  A (dY) as conv_wgrad_tr_kernel: address role = pixel 8*(l>>5) + ((l&15)>>2), channels 16*((l>>4)&1) + 4*(l&3)..+3.
+    // B (patch): address role = pixel j = (l&15)>>2 (+ 8*(l>>5)), tap 8*nb + 4*((l>>4)&1) + (l&3); the lane RECEIVES column l31 = 4 * (tap - 8*nb) + channel
+    const int fp = 8 * hi + ((lane & 15) >> 2);
+    const int fc = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    int boff[5];
+#pragma unroll
+    for (int nb = 0; nb < 5; ++nb) {
+        const int tap = min(8 * nb + 4 * ((lane >> 4) & 1) + (lane & 3), 35);        // columns of taps >= 36 are computed on tap 35 and dropped
+        const int ky = tap / 6, kx = tap - 6 * ky;
+        boff[nb] = (((2 * wave + ky) * SWG_PITCH) + kx + 2 + 2 * fp) * 8;
+    }
+    f32x16 acc[2][5];
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < 5; ++nb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
+
+    __syncthreads();                     // the table
+    if ((int)blockIdx.x < a.ntiles) { load_u8(blockIdx.x); stage_dy(blockIdx.x, 0); }
+    int it = 0;
+    for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x, ++it) {
+        write_patch();                   // every wave left the previous patch at the barrier that ends the loop body
+        et_wait_vmem();                  // this tile's dY has landed
+        __syncthreads();
+        // the next tile's bytes travel behind this tile's MFMAs: the image quads in registers (issued first: the table pass waits for them
+        // alone), dY into the buffer the PREVIOUS tile read (all waves are past its reads: the barrier above)
+        if (tile + (int)gridDim.x < a.ntiles) { load_u8(tile + gridDim.x); stage_dy(tile + gridDim.x, (it + 1) & 1); }
+        const char* const ta = (const char*)(dyl + (it & 1) * SWG_DYV);
+        const char* const tb = (const char*)xl;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            s16x8 af[2], bf[5];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int p = wave * 64 + 16 * ks + 4 * r + fp;
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb) {
+                    const int ch = mb * 32 + fc;
+                    const int off = (p * 8 + ((ch >> 3) ^ tr_swz<8>(p))) * 16 + (ch & 4) * 2;
+                    const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ta + off));
+                    af[mb][4 * r + 0] = v[0]; af[mb][4 * r + 1] = v[1]; af[mb][4 * r + 2] = v[2]; af[mb][4 * r + 3] = v[3];
+                }
+#pragma unroll
+                for (int nb = 0; nb < 5; ++nb) {
+                    const int off = boff[nb] + 2 * (16 * ks + 4 * r) * 8;
+                    const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(tb + off));
+                    bf[nb][4 * r + 0] = v[0]; bf[nb][4 * r + 1] = v[1]; bf[nb][4 * r + 2] = v[2]; bf[nb][4 * r + 3] = v[3];
+                }
+            }
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < 5; ++nb)
+                    acc[mb][nb] = et_mfma32<T>(af[mb], bf[nb], acc[mb][nb]);
+        }
+        __syncthreads();
+    }
+    // ---- the four waves' partial sums meet in wave 0 (LDS, one wave at a time), which adds the real columns into dW
+    et_wait_vmem();
+    float* const red = (float*)dyl;       // [160 registers][64 lanes]
+#pragma unroll 1
+    for (int w = 1; w < 4; ++w) {
+        __syncthreads();
+        if (wave == w) {
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < 5; ++nb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) red[((mb * 5 + nb) * 16 + r) * 64 + lane] = acc[mb][nb][r];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < 5; ++nb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[mb][nb][r] += red[((mb * 5 + nb) * 16 + r) * 64 + lane];
+        }
+    }
+    if (wave != 0 || (l31 & 3) == 3) return;
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int co = mb * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
+#pragma unroll
+            for (int nb = 0; nb < 5; ++nb) {
+                const int tap = 8 * nb + (l31 >> 2);
+                if (co < a.Cout && tap < 36) atomicAdd(a.dw + ((size_t)co * 36 + tap) * 8 + (l31 & 3), acc[mb][nb][r]);
+            }
+        }
 }
 
 // ---- weight gradient of the 3x3 stride-1 layers with BOTH operands shared by the three taps of a kernel row ------------------
@@ -3556,6 +3830,87 @@ extern "C" int et_colsum(const void* x, int dtype, int P, int C, int ld, float* 
     return 0;
 }
 
+// ---- the stem on the loaders' uint8 images (no packed tensor) ------------------------------------------------------------------
+// ET_STEM_U8 (read per call; for the A/B): bit 1 = forward from the uint8 planes, bit 2 = weight gradient from them; default 3, 0 = the packed path
+static int stem_u8_mode(int dtype, int in_is_u8, int C, int IW, int Cout, int KH, int KW, int stride, int pad) {
+    if (!in_is_u8 || C != 3 || (dtype != ET_BF16 && dtype != ET_F16) || KH != 6 || KW != 6 || stride != 2 || pad != 2 || IW % 4 ||
+        Cout > 64 || Cout % 8 || Cout < 8)
+        return 0;
+    return env_int("ET_STEM_U8", 3) & 3;
+}
+template <typename A>
+static int stem_u8_segments(A& a, const void* const* seg_ptrs, const int* seg_counts, int n_segs, int IH, int IW) {
+    if (!seg_ptrs || !seg_counts || n_segs < 1 || n_segs > STEM_MAX_SEGS || IH < 1 || IW < 4 || IW % 4) return -2;
+    int n = 0;
+    for (int s = 0; s < STEM_MAX_SEGS; ++s) {
+        a.seg[s] = s < n_segs ? (const uint8_t*)seg_ptrs[s] : (const uint8_t*)seg_ptrs[0];
+        a.seg_b[s] = s < n_segs ? n : 0x7fffffff;
+        if (s < n_segs) {
+            if (seg_counts[s] < 1 || !seg_ptrs[s] || ((uintptr_t)seg_ptrs[s] & 3)) return -2;      // quads are read as aligned dwords
+            n += seg_counts[s];
+        }
+    }
+    if ((long long)n * 3 * IH * IW >= (1ll << 40)) return -2;
+    return n;
+}
+
+extern "C" int et_conv2d_stem_u8_fwd(const void* const* seg_ptrs, const int* seg_counts, int n_segs, float norm_scale, const void* w,
+                                     void* y, int dtype, int IH, int IW, int Cout, int ldy, const float* scale, const float* bias,
+                                     int act, float* stats, int stats_ld, const void* zero16, et_stream_t stream) {
+    if (!w || !y || !zero16 || !(stem_u8_mode(dtype, 1, 3, IW, Cout, 6, 6, 2, 2) & 1) || ldy < Cout || ldy % 8 || act < 0 || act > 2) return -2;
+    StemArgs a;
+    const int N = stem_u8_segments(a, seg_ptrs, seg_counts, n_segs, IH, IW);
+    if (N < 0) return N;
+    a.norm = norm_scale;
+    a.x = nullptr; a.zero = (const uint16_t*)zero16;      // the weight rows beyond Cout still come from the zero page
+    a.w = (const uint16_t*)w; a.y = (uint16_t*)y;
+    a.N = N; a.IH = IH; a.IW = IW; a.ldx = 8; a.Cout = Cout; a.ldy = ldy;
+    a.OH = (IH + 4 - 6) / 2 + 1; a.OW = (IW + 4 - 6) / 2 + 1;
+    if (a.OH < 1 || a.OW < 1) return -2;
+    a.trn = (a.OH + STEM_TR - 1) / STEM_TR; a.tcn = (a.OW + STEM_TC - 1) / STEM_TC;
+    a.ntiles = N * a.trn * a.tcn;
+    a.scale = scale; a.bias = bias; a.act = act; a.stats = stats; a.stats_ld = stats ? stats_ld : 0;
+    a.stat_rows = (N * a.OH * a.OW + 63) / 64;
+    int grid = env_int("ET_CONV_STEM_WGS", 2 * device_cus());
+    if (grid < 1) grid = 1;
+    if (grid > a.ntiles) grid = a.ntiles;
+    if (stats && !stats_ld && grid > a.stat_rows) grid = a.stat_rows;
+    hipStream_t s = (hipStream_t)stream;
+#define ET_STEM(T_) \
+    do { \
+        if (act == ACT_SILU) hipLaunchKernelGGL((conv_stem_u8_kernel<T_, ACT_SILU>), dim3(grid), dim3(256), 0, s, a); \
+        else if (act == ACT_RELU) hipLaunchKernelGGL((conv_stem_u8_kernel<T_, ACT_RELU>), dim3(grid), dim3(256), 0, s, a); \
+        else hipLaunchKernelGGL((conv_stem_u8_kernel<T_, ACT_NONE>), dim3(grid), dim3(256), 0, s, a); \
+    } while (0)
+    if (dtype == ET_F16) ET_STEM(et_f16); else ET_STEM(uint16_t);
+#undef ET_STEM
+    ET_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int et_conv2d_stem_u8_wgrad(const void* const* seg_ptrs, const int* seg_counts, int n_segs, float norm_scale, const void* dy,
+                                       float* dw, int dtype, int IH, int IW, int Cout, int ldy, const void* zero16, et_stream_t stream) {
+    if (!dy || !dw || !zero16 || !(stem_u8_mode(dtype, 1, 3, IW, Cout, 6, 6, 2, 2) & 2) || ldy < Cout || ldy % 8 || ((uintptr_t)dy & 15)) return -2;
+    StemWgradArgs a;
+    const int N = stem_u8_segments(a, seg_ptrs, seg_counts, n_segs, IH, IW);
+    if (N < 0) return N;
+    a.norm = norm_scale;
+    a.dy = (const uint16_t*)dy; a.zero = (const uint16_t*)zero16; a.dw = dw;
+    a.N = N; a.IH = IH; a.IW = IW; a.ldy = ldy; a.Cout = Cout;
+    a.OH = (IH + 4 - 6) / 2 + 1; a.OW = (IW + 4 - 6) / 2 + 1;
+    if (a.OH < 1 || a.OW < 1) return -2;
+    a.trn = (a.OH + STEM_TR - 1) / STEM_TR; a.tcn = (a.OW + STEM_TC - 1) / STEM_TC;
+    a.ntiles = N * a.trn * a.tcn;
+    int grid = env_int("ET_CONV_STEM_WGS", 2 * device_cus());
+    if (grid < 1) grid = 1;
+    if (grid > a.ntiles) grid = a.ntiles;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == ET_F16) hipLaunchKernelGGL((conv_stem_u8_wgrad_kernel<et_f16>), dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((conv_stem_u8_wgrad_kernel<uint16_t>), dim3(grid), dim3(256), 0, s, a);
+    ET_CHECK_LAUNCH();
+    return 0;
+}
+
 // ---- introspection (tests, bench.py) -----------------------------------------------------------------------
 extern "C" int et_conv2d_kernel_name(int op, int dtype, int N, int IH, int IW, int Cin, int Cout, int KH, int KW, int stride,
                                      int pad, int have_zero_page, int parity_class, char* buf, int buflen) {
@@ -3594,11 +3949,23 @@ extern "C" int et_conv2d_kernel_name(int op, int dtype, int N, int IH, int IW, i
     return 0;
 }
 
+extern "C" int et_conv2d_stem_kernel_name(int op, int dtype, int in_is_u8, int C, int N, int IH, int IW, int Cout, int KH, int KW, int stride,
+                                          int pad, char* buf, int buflen) {
+    // the stem as the MODEL calls it -- an image batch of C planes, uint8 or float -- op 0 = forward, 2 = weight gradient: the uint8
+    // kernels when they take the problem (stem_u8_mode: shape, 16-bit compute type, ET_STEM_U8), else what et_conv2d_kernel_name says
+    // about the packed 8-channel image
+    if (!buf || buflen < 32 || (op != 0 && op != 2)) return -1;
+    const int mode = stem_u8_mode(dtype, in_is_u8, C, IW, Cout, KH, KW, stride, pad);
+    if (op == 0 && (mode & 1)) { snprintf(buf, buflen, "conv_stem_u8_kernel"); return 0; }
+    if (op == 2 && (mode & 2)) { snprintf(buf, buflen, "conv_stem_u8_wgrad_kernel<%s>", dtype == ET_F16 ? "et_f16" : "unsigned short"); return 0; }
+    return et_conv2d_kernel_name(op, dtype, N, IH, IW, 8, Cout, KH, KW, stride, pad, 1, 0, buf, buflen);
+}
+
 extern "C" int et_env_knobs(char* buf, int buflen) {
     // every ET_* runtime knob that is SET in this process's environment, as "NAME=value;..." (bench.py records it).  The complete list:
     // three test hooks (persistent-grid sizes, the BatchNorm finalize form), the experimental buffer-descriptor staging of the row-shift kernels, the opt-in arms that change WHAT runs beside what (step
-    // graph, weight-gradient stream), the data-parallel transport settings, and the experiment-library path.
-    static const char* names[] = {"ET_CONV_S1_WGS", "ET_CONV_STEM_WGS", "ET_CONV_BUF_DMA", "ET_BN_FIN_SMALL", "ET_STEP_GRAPH", "ET_WGRAD_STREAM",
+    // graph, weight-gradient stream, the stem on uint8 planes or on the packed image), the data-parallel transport settings, and the experiment-library path.
+    static const char* names[] = {"ET_CONV_S1_WGS", "ET_CONV_STEM_WGS", "ET_CONV_BUF_DMA", "ET_BN_FIN_SMALL", "ET_STEP_GRAPH", "ET_WGRAD_STREAM", "ET_STEM_U8",
                                   "ET_ALLREDUCE_CHUNK_MB", "ET_ALLREDUCE_DTYPE", "ET_RCCL_CHANNELS", "ET_DP_SINGLE_RANK", "ET_HIP_LIB"};
     if (!buf || buflen < 1) return -1;
     int off = 0;

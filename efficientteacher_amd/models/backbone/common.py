@@ -66,9 +66,17 @@ class Conv(nn.Module):
                                "(model.to('cuda')) before calling it -- there is no CPU path")
         bs = self.bn._et_slot
         act = _act_code(self.act)
+        u8 = None
+        if isinstance(x, ops.U8Images):
+            # the loaders' uint8 images (ops.stem_input): the 6x6 stride-2 stem reads the planes itself, forward (bit 1) and weight
+            # gradient (bit 2); any other first layer -- and ET_STEM_U8=0 -- gets the packed tensor
+            mode = ops.stem_u8_mode(x, cs.w_lp, cs.stride, cs.pad)
+            u8 = x if mode & 2 else None
+            if not mode & 1:
+                x = x.packed()
         if self.bn.training:
             nbt = None if self._et_flat().bulk_nbt else self.bn.num_batches_tracked   # bulk: bumped once per forward
-            return ConvBnActFn.apply(x, residual, self.conv.weight, cs, bs, act, nbt, dst, bn_in, bn_out, acc)
+            return ConvBnActFn.apply(x, residual, self.conv.weight, cs, bs, act, nbt, dst, bn_in, bn_out, acc, u8)
         # eval (EMA teacher): BatchNorm is an affine of the running statistics, folded into the conv epilogue
         flat = self._et_flat()
         o = bs.aff_off

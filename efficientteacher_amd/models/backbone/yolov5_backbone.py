@@ -19,6 +19,7 @@ def _mark_stage(name, t):
 
 
 class YoloV5BackBone(nn.Module):
+    reads_u8_images = True           # forward(x): x may be an ops.U8Images -- stage1 is a Conv, which reads or packs it (common.py Conv.forward)
     supports_concat_dst = True       # forward(dst_c3=, dst_c4=): C3 / C4 written straight into the neck's concat buffers (detector/yolo.py)
 
     def __init__(self, cfg):

@@ -180,8 +180,14 @@ class Model(nn.Module):
         flat.prepare_forward(self.training)
         if not all(t.dim() == 4 and t.shape[1] <= 8 for t in (x if isinstance(x, (list, tuple)) else (x,))):
             raise ValueError("expected an NCHW image batch (B, 3, H, W), or a list of such batches of one shape")
-        # uint8 batches (what the loaders deliver) are normalised inside the pack kernel: x / 255 (ssod_trainer.py:694-696)
-        x8 = ops.pack_input(x, self._compute_dtype, norm_scale=getattr(self, "input_norm_scale", 255.0))
+        # uint8 batches (what the loaders deliver) are normalised where they are read: x / 255 (ssod_trainer.py:694-696) -- by the stem's
+        # own kernels straight from the uint8 planes (ops.U8Images: no packed tensor) when the backbone starts with that stem, else
+        # inside the pack kernel
+        norm = getattr(self, "input_norm_scale", 255.0)
+        if getattr(self.backbone, "reads_u8_images", False):
+            x8 = ops.stem_input(x, self._compute_dtype, norm_scale=norm)
+        else:
+            x8 = ops.pack_input(x, self._compute_dtype, norm_scale=norm)
         slots = None
         # in-place P3 / P4: only a backbone that can write its C3 / C4 outputs into a destination slice (YoloV5BackBone) together
         # with a neck that lays out the concat buffers (YoloV5Neck); any other registered pairing takes the plain path

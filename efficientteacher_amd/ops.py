@@ -48,7 +48,7 @@ class FamilyTimer:
 
     FAMILY = {
         "et_conv2d_fwd": "gather_gemm", "et_conv2d_dgrad": "gather_gemm", "et_conv2d_dgrad_bn": "gather_gemm",
-        "et_conv2d_wgrad": "wgrad", "et_conv2d_wgrad_grouped": "wgrad",
+        "et_conv2d_wgrad": "wgrad", "et_conv2d_wgrad_grouped": "wgrad", "et_conv2d_stem_u8_fwd": "gather_gemm", "et_conv2d_stem_u8_wgrad": "wgrad",
         "et_bn_finalize": "bn", "et_bn_act_fwd": "bn", "et_bn_act_fwd_sharded": "bn", "et_bn_act_bwd_sharded": "bn", "et_bn_act_bwd": "bn", "et_bn_act_bwd_from_partials": "bn", "et_act_bwd": "bn",
         "et_nms": "nms_loss_pl", "et_nms_ssod": "nms_loss_pl", "et_detect_decode": "nms_loss_pl", "et_pseudo_label_transform": "nms_loss_pl",
         "et_select_targets": "nms_loss_pl", "et_yolo_loss": "nms_loss_pl", "et_ota_assign": "nms_loss_pl", "et_score_log_append": "nms_loss_pl",
@@ -203,9 +203,133 @@ def conv_out_hw(ih, iw, k, s, p):
     return (ih + 2 * p - k) // s + 1, (iw + 2 * p - k) // s + 1
 
 
+class U8Images:
+    """The loaders' uint8 NCHW image batches as the input of the stem, in place of the packed (B,H,W,8) tensor: one or more
+    SEGMENTS of whole images of one shape (the labelled and the unlabelled batch of an SSOD step: batch order = segment order, no
+    concatenation), value = byte / norm_scale.  Quacks like that tensor where the layers look (shape, dtype, device); only the stem's
+    own kernels read it (conv2d_fwd / WgradQueue.submit_stem_u8); ``packed()`` is the tensor itself, for every other consumer."""
+    requires_grad = False
+    is_cuda = True
+
+    def __init__(self, parts, dtype, norm_scale):
+        self.parts = [p.contiguous() for p in parts]
+        _, C, H, W = self.parts[0].shape
+        assert all(p.dtype == torch.uint8 and p.shape[1:] == (C, H, W) and p.device == self.parts[0].device for p in self.parts)
+        self.C = C
+        self.shape = torch.Size((sum(p.shape[0] for p in self.parts), H, W, 8))
+        self.dtype, self.device, self.norm_scale = dtype, self.parts[0].device, float(norm_scale)
+        self._packed = None
+
+    def dim(self):
+        return 4
+
+    def packed(self):
+        if self._packed is None:
+            self._packed = pack_input(self.parts, self.dtype, self.norm_scale)
+        return self._packed
+
+    def c_segments(self):
+        n = len(self.parts)
+        import ctypes
+        ptrs = (ctypes.c_void_p * n)(*[_lib.ptr(p) for p in self.parts])
+        counts = (ctypes.c_int * n)(*[p.shape[0] for p in self.parts])
+        return ptrs, counts, n
+
+
+STEM_MAX_SEGS = 4
+
+
+def stem_kernel_name(op, dtype, in_is_u8, C, N, IH, IW, Cout, k, stride, pad):
+    """the kernel the stem of an image batch (C planes, uint8 or float) runs on, op 'fwd' | 'wgrad': conv_stem_u8_kernel /
+    conv_stem_u8_wgrad_kernel<..> when the uint8 path takes it (et_conv2d_stem_kernel_name: shape, 16-bit compute type, the ET_STEM_U8
+    knob -- read per call), else kernel_name() of the packed 8-channel image"""
+    import ctypes
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().et_conv2d_stem_kernel_name({"fwd": 0, "wgrad": 2}[op], _ET_OF[dtype], int(bool(in_is_u8)), C, N, IH, IW, Cout,
+                                                      k, k, stride, pad, buf, 256), "et_conv2d_stem_kernel_name")
+    return buf.value.decode()
+
+
+def stem_input(x, dtype, norm_scale=255.0):
+    """What the model hands its first layer: U8Images when the batch(es) are what the uint8 stem kernels read (uint8 NCHW, 3 planes,
+    rows of whole pixel quads, at most STEM_MAX_SEGS segments, a 16-bit compute type); the packed tensor (pack_input) for everything
+    else -- float images, fp32 parity mode, other channel counts.  Whether the first layer really IS the 6x6 stride-2 stem is the
+    layer's own decision (models/backbone/common.py Conv.forward packs a U8Images it cannot read)."""
+    parts = list(x) if isinstance(x, (list, tuple)) else [x]
+    if (dtype in LP_DTYPES and len(parts) <= STEM_MAX_SEGS
+            and all(p.dtype == torch.uint8 and p.dim() == 4 and p.shape[1] == 3 and p.shape[3] % 4 == 0 and (p.is_cuda or _lib.is_emulated())
+                    and p.shape[0] > 0 and p.shape[1:] == parts[0].shape[1:] for p in parts)):
+        u8 = U8Images(parts, dtype, norm_scale)
+        if all(p.data_ptr() % 4 == 0 for p in u8.parts):
+            return u8
+    return pack_input(x, dtype, norm_scale=norm_scale)
+
+
+def stem_u8_mode(u8, w, stride, pad):
+    """bit 1: conv2d_fwd reads the uint8 planes; bit 2: so does the weight gradient (0: this layer is not the stem, or ET_STEM_U8 = 0)"""
+    N, IH, IW, _ = u8.shape
+    Cout, KH, KW, Cin = w.shape
+    if KH != KW or Cin != 8:
+        return 0
+    a = (u8.dtype, True, u8.C, N, IH, IW, Cout, KH, stride, pad)
+    return (1 if stem_kernel_name("fwd", *a) == "conv_stem_u8_kernel" else 0) | \
+           (2 if stem_kernel_name("wgrad", *a).startswith("conv_stem_u8_wgrad_kernel") else 0)
+
+
+def _stem_u8_fwd(u8, w, stride, pad, scale, bias, act, out, want_stats, shards):
+    N, IH, IW, _ = u8.shape
+    Cout = w.shape[0]
+    assert w.is_contiguous() and w.dtype == u8.dtype and tuple(w.shape[1:]) == (6, 6, 8) and stride == 2 and pad == 2
+    OH, OW = conv_out_hw(IH, IW, 6, 2, 2)
+    if out is None:
+        out = torch.empty((N, OH, OW, Cout), dtype=u8.dtype, device=u8.device)
+    assert out.shape == (N, OH, OW, Cout)
+    stats, stats_ld = None, 0
+    if shards is not None:
+        assert not want_stats
+        stats, stats_ld = shards
+    if want_stats:
+        stats = torch.empty((stats_rows("fwd", u8.dtype, N, IH, IW, 8, Cout, 6, 2, 2), 2, Cout), dtype=torch.float32, device=u8.device)
+    ev = TIMER.span("conv_stem_u8_kernel", 2.0 * N * OH * OW * Cout * 3 * 36,
+                    nbytes=N * 3 * IH * IW + (N * OH * OW * Cout + w.numel()) * w.element_size(),
+                    shape=("fwd", N, IH, IW, 3, Cout, 6, 2)) if TIMER else None
+    if ev:
+        ev[0].record()
+    ptrs, counts, n = u8.c_segments()
+    _lib.check(_lib.load().et_conv2d_stem_u8_fwd(ptrs, counts, n, u8.norm_scale, _lib.ptr(w), _lib.ptr(out), et_dtype(w), IH, IW, Cout,
+                                                 _nhwc(out), _lib.ptr(scale), _lib.ptr(bias), act, _lib.ptr(stats), stats_ld,
+                                                 _lib.ptr(zero_page(u8.device)), _lib.stream(out)), "et_conv2d_stem_u8_fwd")
+    if ev:
+        ev[1].record()
+    return (out, stats) if want_stats else out
+
+
+def stem_u8_wgrad(u8, dy, dw):
+    """dw (Cout, 6, 6, 8) fp32 += the stem's weight gradient from dY and the uint8 planes (channels 0..2 of every tap; the pad slots
+    are not touched)"""
+    N, IH, IW, _ = u8.shape
+    _, OH, OW, Cout = dy.shape
+    assert dy.dtype == u8.dtype and dy.shape[:3] == (N,) + conv_out_hw(IH, IW, 6, 2, 2)
+    assert dw.dtype == torch.float32 and dw.is_contiguous() and dw.shape == (Cout, 6, 6, 8)
+    ev = TIMER.span(stem_kernel_name("wgrad", u8.dtype, True, 3, N, IH, IW, Cout, 6, 2, 2), 2.0 * N * OH * OW * Cout * 3 * 36, 1,
+                    nbytes=N * 3 * IH * IW + N * OH * OW * Cout * dy.element_size() + 8 * Cout * 108,
+                    shape=("wgrad", N, IH, IW, 3, Cout, 6, 2)) if TIMER else None
+    if ev:
+        ev[0].record()
+    ptrs, counts, n = u8.c_segments()
+    _lib.check(_lib.load().et_conv2d_stem_u8_wgrad(ptrs, counts, n, u8.norm_scale, _lib.ptr(dy), _lib.ptr(dw), et_dtype(dy), IH, IW, Cout,
+                                                   _nhwc(dy), _lib.ptr(zero_page(dy.device)), _lib.stream(dy)), "et_conv2d_stem_u8_wgrad")
+    if ev:
+        ev[1].record()
+
+
 def conv2d_fwd(x, w, stride, pad, *, scale=None, bias=None, act=ACT_NONE, residual=None, out=None, want_stats=False, shards=None):
     """y = act(conv(x, w) * scale + bias) + residual ; optional BN partial statistics (rows, 2, Cout) -- or, with shards = (tensor
-    whose first element is this layer's channel 0 of a zeroed [BN_SHARDS][2][ld] accumulator, ld), ADDED into that accumulator."""
+    whose first element is this layer's channel 0 of a zeroed [BN_SHARDS][2][ld] accumulator, ld), ADDED into that accumulator.
+    x may be a U8Images (the stem on the loaders' uint8 planes; the layer has checked stem_u8_mode)."""
+    if isinstance(x, U8Images):
+        assert residual is None
+        return _stem_u8_fwd(x, w, stride, pad, scale, bias, act, out, want_stats, shards)
     N, IH, IW, Cin = x.shape
     Cout, KH, KW, Cin2 = w.shape
     assert Cin == Cin2 and w.is_contiguous() and w.dtype == x.dtype
@@ -313,6 +437,34 @@ class WgradQueue:
         self.last[key] = self.tick
         if len(lst) >= self.group:
             self._flush_key(key)
+
+    def submit_stem_u8(self, u8, dy, dw, on_done=None):
+        """the stem's weight gradient from the uint8 planes (stem_u8_wgrad): a single launch outside the groups -- at once, on the side
+        stream under the same rule as a grouped k > 1 launch.  The images are read HERE, at the end of backward: the side stream is
+        recorded on them (caching allocator), and the launching stream joins the side stream at the end of the pass like for any group."""
+        dev = dy.device
+        side_ok = dev.type == "cuda" and self.use_side in (1, 3)
+        if side_ok and not self._cb_armed:
+            try:
+                torch.autograd.Variable._execution_engine.queue_callback(self.flush)
+                self._cb_armed = True
+            except RuntimeError:         # not inside a backward pass: nobody would join the side stream
+                side_ok = False
+        if side_ok:
+            main, side = torch.cuda.current_stream(dev), self.side_stream(dev)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                stem_u8_wgrad(u8, dy, dw)
+                dy.record_stream(side)
+                for p in u8.parts:
+                    p.record_stream(side)
+                if on_done is not None:
+                    on_done()
+            self._dirty.add(dev)
+            return
+        stem_u8_wgrad(u8, dy, dw)
+        if on_done is not None:
+            on_done()
 
     def _flush_key(self, key):
         lst = self.pending.pop(key, None)

@@ -31,7 +31,7 @@ enum { ET_F32 = 0, ET_BF16 = 1, ET_F16 = 2 };   /* ET_F16 (r05): IEEE half stora
  * for ("gfx950") and the ABI version.  ET_ABI_VERSION changes whenever an entry point is added or a signature / workspace
  * contract changes; a binding must refuse a library whose et_abi_version() differs from the header it was written against
  * (efficientteacher_amd/_lib.py does): a stale libet_hip.so would otherwise read e.g. a new int argument as the stream. */
-#define ET_ABI_VERSION 7
+#define ET_ABI_VERSION 8
 const char* et_build_arch(void);
 int et_abi_version(void);
 
@@ -233,6 +233,24 @@ int et_weight_transpose(const void* w, void* wT, int dtype, int Cout, int taps, 
 int et_conv2d_kernel_name(int op, int dtype, int N, int IH, int IW, int Cin, int Cout, int KH, int KW, int stride,
                           int pad, int have_zero_page, int parity_class, char* buf /*host out*/, int buflen);
 int et_env_knobs(char* buf /*host out*/, int buflen);
+/* The stem (6x6 stride 2 pad 2, 3 -> Cout <= 64 channels, 16-bit compute types) straight from the loaders' uint8 NCHW images: no packed
+ * (B,H,W,8) tensor exists.  The batch is up to four SEGMENTS of whole images (seg_ptrs / seg_counts: HOST arrays of n_segs device
+ * pointers, 4-byte aligned, and image counts; segment order = batch order: the labelled and the unlabelled images of an SSOD step
+ * without a concatenation).  IW % 4 == 0.  A pixel value is T(byte / norm_scale), bit-equal to et_pack_input_u8.
+ *   et_conv2d_stem_u8_fwd: y / stats / scale / bias / act as et_conv2d_fwd (w: (Cout, 6, 6, 8), the packed layer's weight); the result is
+ *       bit-identical to et_pack_input_u8 + et_conv2d_fwd.
+ *   et_conv2d_stem_u8_wgrad: dw (Cout, 6, 6, 8) fp32 += the weight gradient; only channels 0..2 of every tap are written (the pad
+ *       slots keep their contents).  The images must stay unchanged until this launch has run.
+ *   et_conv2d_stem_kernel_name: the kernel the stem of an image batch (C planes, uint8 or not) runs on, op 0 = forward, 2 = weight
+ *       gradient: one of the kernels above, or et_conv2d_kernel_name's answer for the packed image.  -2 from the two launchers = not
+ *       this path's problem (shape, dtype, or ET_STEM_U8 -- bit 1 forward, bit 2 weight gradient, default 3 -- switches it off). */
+int et_conv2d_stem_u8_fwd(const void* const* seg_ptrs, const int* seg_counts, int n_segs, float norm_scale, const void* w, void* y,
+                          int dtype, int IH, int IW, int Cout, int ldy, const float* scale, const float* bias, int act,
+                          float* stats_partial, int stats_ld, const void* zero16, et_stream_t stream);
+int et_conv2d_stem_u8_wgrad(const void* const* seg_ptrs, const int* seg_counts, int n_segs, float norm_scale, const void* dy, float* dw,
+                            int dtype, int IH, int IW, int Cout, int ldy, const void* zero16, et_stream_t stream);
+int et_conv2d_stem_kernel_name(int op, int dtype, int in_is_u8, int C, int N, int IH, int IW, int Cout, int KH, int KW, int stride,
+                               int pad, char* buf /*host out*/, int buflen);
 /* every layer of a flat weight arena at once: table = n_layers x {element offset, Cout, taps, Cin} (int32, device,
  * sorted by offset); wT_arena has the arena's layout with each layer stored (Cin, taps, Cout). */
 int et_weight_transpose_all(const void* w_arena, void* wT_arena, int dtype, const int* table, int n_layers,
