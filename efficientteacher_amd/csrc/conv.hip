@@ -2121,43 +2121,6 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(StemArgs a) { conv_st
 template <typename T, int ACT>
 __global__ __launch_bounds__(256, 2) void conv_stem_u8_kernel(StemArgs a) { conv_stem_body<T, ACT, true>(a); }
 
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-static int device_cus() {
-    static const int n_cu = [] { hipDeviceProp_t p; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }();
-    return n_cu;
-}
-
-// shape gate + launch; returns 1 if the stem kernel took the problem
-static int try_launch_stem(const void* x, const void* w, void* y, int dtype, int N, int IH, int IW, int Cin, int ldx, int Cout,
-                           int KH, int KW, int stride, int pad, int ldy, const float* scale, const float* bias, int act,
-                           const void* residual, float* stats, int stats_ld, const void* zero16, hipStream_t s, bool launch) {
-    if ((dtype != ET_BF16 && dtype != ET_F16) || KH != 6 || KW != 6 || stride != 2 || pad != 2 || Cin != 8 || Cout > 64 || Cout % 8 ||
-        residual || !zero16)
-        return 0;
-    if (!launch) return 1;
-    StemArgs a;
-    a.x = (const uint16_t*)x; a.w = (const uint16_t*)w; a.y = (uint16_t*)y; a.zero = (const uint16_t*)zero16;
-    a.N = N; a.IH = IH; a.IW = IW; a.ldx = ldx; a.Cout = Cout; a.ldy = ldy;
-    a.OH = (IH + 2 * pad - KH) / stride + 1; a.OW = (IW + 2 * pad - KW) / stride + 1;
-    a.trn = (a.OH + STEM_TR - 1) / STEM_TR; a.tcn = (a.OW + STEM_TC - 1) / STEM_TC;
-    a.ntiles = N * a.trn * a.tcn;
-    a.scale = scale; a.bias = bias; a.act = act; a.stats = stats; a.stats_ld = stats ? stats_ld : 0;
-    a.stat_rows = (N * a.OH * a.OW + 63) / 64;        // == et_conv2d_stats_rows
-    int grid = env_int("ET_CONV_STEM_WGS", 2 * device_cus());      // read per launch: tests shrink it to exercise the tile loop
-    if (grid < 1) grid = 1;
-    if (grid > a.ntiles) grid = a.ntiles;
-    if (stats && !stats_ld && grid > a.stat_rows) grid = a.stat_rows;
-#define ET_STEM(T_) \
-    do { \
-        if (act == ACT_SILU) hipLaunchKernelGGL((conv_stem_kernel<T_, ACT_SILU>), dim3(grid), dim3(256), 0, s, a); \
-        else if (act == ACT_RELU) hipLaunchKernelGGL((conv_stem_kernel<T_, ACT_RELU>), dim3(grid), dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL((conv_stem_kernel<T_, ACT_NONE>), dim3(grid), dim3(256), 0, s, a); \
-    } while (0)
-    if (dtype == ET_F16) ET_STEM(et_f16); else ET_STEM(uint16_t);
-#undef ET_STEM
-    return 1;
-}
-
 // ---- wgrad ----------------------------------------------------------------------------------------
 struct WgradGeom {
     int N, IH, IW, Cin, ldx;     // X (gathered operand)
@@ -3120,6 +3083,20 @@ __global__ __launch_bounds__(256) void colsum_vec8_kernel(const T* __restrict__ 
     }
 }
 
+// ---- host layer -------------------------------------------------------------------------------------------------------------
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static int device_cus() {
+    static const int n_cu = [] { hipDeviceProp_t p; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }();
+    return n_cu;
+}
+
+// f(TypeTag<T>) for the storage type of an ET_* dtype; false for any other value (launch_gemm / launch_wgrad: all three types)
+template <typename T> struct TypeTag { using type = T; };
+template <typename F> static bool with_dtype(int dtype, F&& f) {
+    if (dtype == ET_F32) f(TypeTag<float>{}); else if (dtype == ET_BF16) f(TypeTag<uint16_t>{}); else if (dtype == ET_F16) f(TypeTag<et_f16>{}); else return false;
+    return true;
+}
+
 static int fill_common(GatherGeom& g, int N, int IH, int IW, int Cin, int ldx, int QH, int QW, int OH, int OW,
                        int Cout, int ldy, int vec) {
     if (Cin % vec) return -2;
@@ -3205,28 +3182,76 @@ static bool rs_eligible(const GatherGeom& g, int BM, int unit_rows) {
         if (g.dy[t] != sgn * (t / 3 - 1) || g.dx[t] != sgn * (t % 3 - 1) || g.wt[t] != t) return false;
     return true;
 }
-struct GemmPlan { int kind, BM, BN, WM, WN, BKV, NS; bool utap; int wgs, kc, tn, full; };   // wgs / kc / tn / full: conv1x1_stream_kernel only
 
-// conv1x1_stream_kernel's shape table (its header explains the register budget behind it).  full = the launch needs residual /
-// accumulate / BN-backward sums in the epilogue.
-static GemmPlan plan_s1(const GatherGeom& g, bool full) {
-    const int BN = g.Cout > 128 ? 256 : (g.Cout > 64 ? 128 : 64);
-    const int kc = g.Cin / 64;
-    GemmPlan p{GEMM_S1, 0, BN, 0, 0, 8, 0, true, 2, kc, 2, full ? 1 : 0};
-    if (full && kc == 4) {               // eight waves, 32-channel wave tiles, one workgroup per CU
-        p.tn = 1; p.WN = BN / 32; p.WM = BN == 256 ? 1 : (BN == 128 ? 2 : 4); p.BM = 32 * p.WM; p.wgs = 1;
-        p.NS = p.BM == 32 ? 16 : (p.BM == 64 ? 10 : 5);
-        return p;
-    }
-    p.WN = BN / 64;
-    p.WM = BN == 256 ? 1 : (BN == 128 ? 2 : 4);                              // four waves
-    const int tmw = (kc == 4 || full || BN == 64) ? 1 : 2;                   // rows per wave = 32 * tmw
-    p.BM = 32 * tmw * p.WM;
-    p.NS = p.BM == 32 ? 8 : (p.BM == 64 ? 6 : 3);                            // ring: 8 x 4 KB / 6 x 8 KB / 3 x 16 KB beside the 16-row slabs
-    return p;
+// ---- the instantiations: ONE row list per kernel family (a row = the template arguments after T) --------------------------------
+// Each list is expanded twice: into a table of GemmPlan rows, which the plan functions search and plan_name / s1_grid / the
+// statistics-row count read, and into launch_gemm's dispatch, which instantiates the row at the same index.  A plan IS a pointer to a
+// table row: the name reported and the kernel launched cannot describe different tuples.
+//      conv1x1_stream_kernel (+ _flat twin; its header explains the register budget): K/64 WN TN WM TMW NS WGS FULL (= residual /
+//      accumulate / BN-backward sums in the epilogue)
+#define ET_S1_ROWS \
+    ET_S1(4, 4, 2, 1, 1, 8, 2, false)  /* four waves, 64-channel wave tiles, two workgroups per CU */ \
+    ET_S1(4, 2, 2, 2, 1, 6, 2, false)  \
+    ET_S1(2, 4, 2, 1, 2, 6, 2, false)  /* ring: 8 x 4 KB / 6 x 8 KB / 3 x 16 KB beside the 16-row slabs */ \
+    ET_S1(2, 2, 2, 2, 2, 3, 2, false)  \
+    ET_S1(2, 1, 2, 4, 1, 3, 2, false)  \
+    ET_S1(1, 4, 2, 1, 2, 6, 2, false)  \
+    ET_S1(1, 2, 2, 2, 2, 3, 2, false)  \
+    ET_S1(1, 1, 2, 4, 1, 3, 2, false)  \
+    ET_S1(4, 8, 1, 1, 1, 16, 1, true)  /* eight waves, 32-channel wave tiles, one workgroup per CU */ \
+    ET_S1(4, 4, 1, 2, 1, 10, 1, true)  \
+    ET_S1(2, 4, 2, 1, 1, 8, 2, true)   \
+    ET_S1(2, 2, 2, 2, 1, 6, 2, true)   \
+    ET_S1(2, 1, 2, 4, 1, 3, 2, true)   \
+    ET_S1(1, 4, 2, 1, 1, 8, 2, true)   \
+    ET_S1(1, 2, 2, 2, 1, 6, 2, true)   \
+    ET_S1(1, 1, 2, 4, 1, 3, 2, true)
+//      conv_gemm_glds_kernel: BM BN WM WN BKV NS UTAP (NS = 3, the short-K ring: 16-bit types only)
+#define ET_GLDS_ROWS \
+    ET_GLDS(128, 128, 2, 2, 4, 3, true)  ET_GLDS(128, 64, 2, 2, 4, 3, true)  /* short-K: 32-wide chunks, 3-deep ring */ \
+    ET_GLDS(128, 128, 2, 2, 8, 2, true)  ET_GLDS(128, 64, 2, 2, 8, 2, true)  \
+    ET_GLDS(128, 128, 2, 2, 4, 2, true)  ET_GLDS(128, 64, 2, 2, 4, 2, true)  \
+    ET_GLDS(128, 128, 2, 2, 4, 2, false) ET_GLDS(128, 64, 2, 2, 4, 2, false)
+//      conv_gemm_kernel: BM BN WM WN BKV UTAP
+#define ET_REG_ROWS \
+    ET_REG(128, 128, 2, 2, 8, true)  ET_REG(128, 64, 2, 2, 8, true)  \
+    ET_REG(128, 128, 2, 2, 4, true)  ET_REG(128, 64, 2, 2, 4, true)  \
+    ET_REG(128, 128, 2, 2, 4, false) ET_REG(128, 64, 2, 2, 4, false)
+//      conv_gemm_rs_kernel (+ its _flat twin): BM BN WM WN
+#define ET_RS_ROWS ET_RS(128, 128, 2, 2) ET_RS(128, 64, 2, 2)
+
+struct GemmPlan { int kind, BM, BN, WM, WN, BKV, NS; bool utap; int wgs, kc, tn, full; };   // wgs / kc / tn / full: conv1x1_stream_kernel only
+#define ET_S1(KC_, WN_, TN_, WM_, TMW_, NS_, WGS_, FULL_) {GEMM_S1, 32 * TMW_ * WM_, 32 * TN_ * WN_, WM_, WN_, 8, NS_, true, WGS_, KC_, TN_, FULL_},
+#define ET_GLDS(BM_, BN_, WM_, WN_, BKV_, NS_, UT_) {GEMM_GLDS, BM_, BN_, WM_, WN_, BKV_, NS_, UT_, 0, 0, 0, 0},
+#define ET_REG(BM_, BN_, WM_, WN_, BKV_, UT_) {GEMM_REG, BM_, BN_, WM_, WN_, BKV_, 2, UT_, 0, 0, 0, 0},
+#define ET_RS(BM_, BN_, WM_, WN_) {GEMM_RS, BM_, BN_, WM_, WN_, 8, 2, true, 0, 0, 0, 0},
+static const GemmPlan s1_rows[] = {ET_S1_ROWS};
+static const GemmPlan glds_rows[] = {ET_GLDS_ROWS};
+static const GemmPlan reg_rows[] = {ET_REG_ROWS};
+static const GemmPlan rs_rows[] = {ET_RS_ROWS};
+#undef ET_S1
+#undef ET_GLDS
+#undef ET_REG
+#undef ET_RS
+static const GemmPlan pp_row{GEMM_PP, 256, 256, 2, 4, 8, 2, true, 0, 0, 0, 0};       // conv_gemm_pp_kernel<T>, conv_gemm_pprs_kernel<T>:
+static const GemmPlan pprs_row{GEMM_PPRS, 256, 256, 2, 4, 8, 2, true, 0, 0, 0, 0};   // one instantiation per type
+
+// the row of a family's table that pred accepts; null = no such instantiation (the launch then fails with -2)
+template <typename Row, size_t N, typename Pred> static const Row* find_row(const Row (&rows)[N], Pred pred) {
+    for (const Row& r : rows)
+        if (pred(r)) return &r;
+    return nullptr;
 }
 
-static GemmPlan plan_gemm(const GatherGeom& g, int elem_bytes, bool have_zero_page, bool full_epilogue = false) {
+// conv1x1_stream_kernel: the row by K, column tile and epilogue.  full = the launch needs residual / accumulate / BN-backward sums
+// in the epilogue.
+static const GemmPlan* plan_s1(const GatherGeom& g, bool full) {
+    const int BN = g.Cout > 128 ? 256 : (g.Cout > 64 ? 128 : 64);
+    const int kc = g.Cin / 64;
+    return find_row(s1_rows, [&](const GemmPlan& r) { return r.kc == kc && r.BN == BN && (r.full != 0) == full; });
+}
+
+static const GemmPlan* plan_gemm(const GatherGeom& g, int elem_bytes, bool have_zero_page, bool full_epilogue = false) {
     // Build-time constants that were tuning knobs in r01 / r02 (swept on the step, profiles/r02_step_knob_sweep*_same_box.log, and
     // per layer, profiles/r02_microbench_narrow_k.log): GEMMs with K <= 128 elements use the 128x64 tile (3 workgroups per CU for
     // the HBM-bound short-K 1x1 layers; at K = 256 the 128-wide tile re-reads the activations half as often: 150 -> 124 us on
@@ -3237,8 +3262,14 @@ static GemmPlan plan_gemm(const GatherGeom& g, int elem_bytes, bool have_zero_pa
     const bool bf16 = elem_bytes == 2;
     const bool wide = g.Cout > 64 && !(narrow_k > 0 && g.T * g.Cin <= narrow_k);
     const bool glds = have_zero_page;
-    GemmPlan p{glds ? GEMM_GLDS : GEMM_REG, 128, wide ? 128 : 64, 2, 2, g.CV % 8 == 0 ? 8 : 4, 2, g.CV % 4 == 0, 0, 0, 0, 0};
-    if (!(bf16 && glds && g.CV % 8 == 0)) return p;
+    const int BN = wide ? 128 : 64, BKV = g.CV % 8 == 0 ? 8 : 4;
+    const bool utap = g.CV % 4 == 0;
+    // the 128-row tile of either staging form: NS-deep ring of BKV-vector chunks (the register-staged kernel has no ring: NS = 2)
+    const auto tiled = [&](int bkv, int ns) {
+        const auto want = [&](const GemmPlan& r) { return r.BM == 128 && r.BN == BN && r.BKV == bkv && r.NS == ns && r.utap == utap; };
+        return glds ? find_row(glds_rows, want) : find_row(reg_rows, want);
+    };
+    if (!(bf16 && glds && g.CV % 8 == 0)) return tiled(BKV, 2);
     // 1x1 layers with K <= 256 and <= 256 output channels: the persistent streaming kernel, also for the dgrads with a residual /
     // accumulate / BN-backward sums in the epilogue.  Measured (profiles/r04_mb_1x1_stream_kernel_ab.txt, r04_stream_full_and_fuse_ab_current_build.txt): plain layers
     // 4.4-5.3 TB/s against 3.7-5.1 of the tiled kernels (128->128 @80x80: 54 -> 46 us, 256->256 @80x80: 111 -> 86-97 us); step, same
@@ -3250,7 +3281,8 @@ static GemmPlan plan_gemm(const GatherGeom& g, int elem_bytes, bool have_zero_pa
     // short-K GEMMs (K <= 256, i.e. <= 4 chunks of 64) run 32-wide chunks in a 3-deep ring -- 48 KB of LDS, three
     // workgroups per CU, two chunks in flight each (measured 3-10 % on the 1x1 layers); everything else the 64-wide
     // double buffer (deeper rings or taller 4-wave tiles cost occupancy and lose: profiles/)
-    int ring = g.T * g.Cin <= 256 ? 12843 : 12882;
+    enum { RING_SHORT_K, RING_128, RING_256 };
+    int ring = g.T * g.Cin <= 256 ? RING_SHORT_K : RING_128;
     // 8-wave 256x256 tile (one workgroup per CU, half the L2->LDS bytes per flop): 3x3 layers with >= 256 output
     // channels, and deep 1x1 layers when the grid fills whole residency rounds reasonably
     if (g.Cout >= 256) {
@@ -3261,17 +3293,12 @@ static GemmPlan plan_gemm(const GatherGeom& g, int elem_bytes, bool have_zero_pa
         // (a grid that leaves most CUs without a 256x256 tile -- the teacher's 32-image 20x20 layers: 100 tiles -- still runs it: 128x128
         // tiles for such grids won isolated and lost on the step three times, profiles/r02_microbench_big_tile_minfill.log,
         // r03_big_tile_minfill_ab.txt, NOTEBOOK.md round 4: the 256x256 tile costs less CU-time and the other stream fills the rest)
-        if (g.TT > 1 || (g.T * g.Cin >= 512 && fills)) ring = 25680;
+        if (g.TT > 1 || (g.T * g.Cin >= 512 && fills)) ring = RING_256;
     }
     // 3x3 stride-1 layers on the 128-row tiles: activation rows shared by the three taps of a kernel row
-    if (ring == 12882 && rs_eligible(g, 128, RS_A_ROWS(128))) return GemmPlan{GEMM_RS, 128, wide ? 128 : 64, 2, 2, 8, 2, true, 0, 0, 0, 0};
-    if (ring == 25680 && rs_eligible(g, 256, PPRS_ROWS)) return GemmPlan{GEMM_PPRS, 256, 256, 2, 4, 8, 2, true, 0, 0, 0, 0};
-    switch (ring) {
-        case 25680: p = GemmPlan{GEMM_PP, 256, 256, 2, 4, 8, 2, true, 0, 0, 0, 0}; break;
-        case 12843: p.BKV = 4; p.NS = 3; break;
-        default: break;
-    }
-    return p;
+    if (ring == RING_128 && rs_eligible(g, 128, RS_A_ROWS(128))) return find_row(rs_rows, [&](const GemmPlan& r) { return r.BM == 128 && r.BN == BN; });
+    if (ring == RING_256) return rs_eligible(g, 256, PPRS_ROWS) ? &pprs_row : &pp_row;
+    return ring == RING_SHORT_K ? tiled(4, 3) : tiled(BKV, 2);
 }
 
 // the name rocprofv3 prints for the plan's kernel (template arguments spelled as the demangler does)
@@ -3299,60 +3326,45 @@ template <typename T>
 static int launch_gemm(const void* X, const void* W, void* Y, const void* zero16, GatherGeom g, const Epilogue& ep,
                        hipStream_t s) {
     if (g.M <= 0) return 0;
-    const int nfast = 1;
-    g.nfast = nfast;
-    const GemmPlan p = plan_gemm(g, (int)sizeof(T), zero16 != nullptr, ep.res != nullptr || ep.accumulate || ep.bn_y != nullptr);
+    g.nfast = 1;
+    const GemmPlan* const pp = plan_gemm(g, (int)sizeof(T), zero16 != nullptr, ep.res != nullptr || ep.accumulate || ep.bn_y != nullptr);
+    if (!pp) return -2;
+    const GemmPlan& p = *pp;
     g.ntm = (g.M + p.BM - 1) / p.BM;
     g.ntn = (g.Cout + p.BN - 1) / p.BN;
     const T* x = (const T*)X; const T* w = (const T*)W; T* y = (T*)Y; const T* z = (const T*)zero16;
     const dim3 grid(g.ntm * g.ntn), block(64 * p.WM * p.WN);
+    // the row lists again, as launches: expansion i instantiates row i of the family's table, and the plan points at its row
+    int i = 0;
+#define ET_TWINS(BUF_, GRID_, KERN_, FLAT_) \
+    { if (BUF_) hipLaunchKernelGGL(KERN_, GRID_, block, 0, s, x, w, y, z, g, ep); else hipLaunchKernelGGL(FLAT_, GRID_, block, 0, s, x, w, y, z, g, ep); return 0; }
+    if (p.kind == GEMM_REG) {
+#define ET_REG(BM_, BN_, WM_, WN_, BKV_, UT_) \
+    if (pp == &reg_rows[i++]) { hipLaunchKernelGGL((conv_gemm_kernel<T, BM_, BN_, WM_, WN_, BKV_, UT_>), grid, block, 0, s, x, w, y, g, ep); return 0; }
+        ET_REG_ROWS
+#undef ET_REG
+    }
+    if (p.kind == GEMM_GLDS) {
 #define ET_GLDS(BM_, BN_, WM_, WN_, BKV_, NS_, UT_) \
-    hipLaunchKernelGGL((conv_gemm_glds_kernel<T, BM_, BN_, WM_, WN_, BKV_, NS_, UT_>), grid, block, 0, s, x, w, y, z, g, ep)
-#define ET_REG(BN_, BKV_, UT_) \
-    hipLaunchKernelGGL((conv_gemm_kernel<T, 128, BN_, 2, 2, BKV_, UT_>), grid, block, 0, s, x, w, y, g, ep)
-    const int key = p.BM * 100000 + p.BN * 100 + p.BKV * 10 + p.NS;
-    if (p.kind == GEMM_S1) {
-        if constexpr (sizeof(T) == 2) {
+    if constexpr (NS_ == 2 || sizeof(T) == 2) if (pp == &glds_rows[i]) { hipLaunchKernelGGL((conv_gemm_glds_kernel<T, BM_, BN_, WM_, WN_, BKV_, NS_, UT_>), grid, block, 0, s, x, w, y, z, g, ep); return 0; } \
+    ++i;
+        ET_GLDS_ROWS
+#undef ET_GLDS
+    }
+    if constexpr (sizeof(T) == 2) {
+        if (p.kind == GEMM_S1) {
             const dim3 sgrid(s1_grid(g.ntm, p));
             const bool s1buf = env_int("ET_CONV_BUF_DMA", 1) && (size_t)g.M * g.ldx * sizeof(T) < (1ull << 31);
-#define ET_S1(KC_, WN_, TN_, WM_, TMW_, NS_, WGS_, FULL_)                                                                                     \
-    do {                                                                                                                                      \
-        if (s1buf) hipLaunchKernelGGL((conv1x1_stream_kernel<T, KC_, WN_, TN_, WM_, TMW_, NS_, WGS_, FULL_>), sgrid, block, 0, s, x, w, y, z, g, ep);       \
-        else hipLaunchKernelGGL((conv1x1_stream_flat_kernel<T, KC_, WN_, TN_, WM_, TMW_, NS_, WGS_, FULL_>), sgrid, block, 0, s, x, w, y, z, g, ep);   \
-    } while (0)
-            switch ((p.full ? 10000 : 0) + p.kc * 1000 + p.BN) {
-                //            K/64 WN TN WM TMW NS WGS
-                case 4256: ET_S1(4, 4, 2, 1, 1, 8, 2, false); return 0;
-                case 4128: ET_S1(4, 2, 2, 2, 1, 6, 2, false); return 0;
-                case 2256: ET_S1(2, 4, 2, 1, 2, 6, 2, false); return 0;
-                case 2128: ET_S1(2, 2, 2, 2, 2, 3, 2, false); return 0;
-                case 2064: ET_S1(2, 1, 2, 4, 1, 3, 2, false); return 0;
-                case 1256: ET_S1(1, 4, 2, 1, 2, 6, 2, false); return 0;
-                case 1128: ET_S1(1, 2, 2, 2, 2, 3, 2, false); return 0;
-                case 1064: ET_S1(1, 1, 2, 4, 1, 3, 2, false); return 0;
-                case 14256: ET_S1(4, 8, 1, 1, 1, 16, 1, true); return 0;
-                case 14128: ET_S1(4, 4, 1, 2, 1, 10, 1, true); return 0;
-                case 12256: ET_S1(2, 4, 2, 1, 1, 8, 2, true); return 0;
-                case 12128: ET_S1(2, 2, 2, 2, 1, 6, 2, true); return 0;
-                case 12064: ET_S1(2, 1, 2, 4, 1, 3, 2, true); return 0;
-                case 11256: ET_S1(1, 4, 2, 1, 1, 8, 2, true); return 0;
-                case 11128: ET_S1(1, 2, 2, 2, 1, 6, 2, true); return 0;
-                case 11064: ET_S1(1, 1, 2, 4, 1, 3, 2, true); return 0;
-                default: return -2;
-            }
+#define ET_S1(KC_, WN_, TN_, WM_, TMW_, NS_, WGS_, FULL_) \
+    if (pp == &s1_rows[i++]) ET_TWINS(s1buf, sgrid, (conv1x1_stream_kernel<T, KC_, WN_, TN_, WM_, TMW_, NS_, WGS_, FULL_>), (conv1x1_stream_flat_kernel<T, KC_, WN_, TN_, WM_, TMW_, NS_, WGS_, FULL_>))
+            ET_S1_ROWS
 #undef ET_S1
         }
-        return -2;
-    }
-    if (p.kind == GEMM_PP) {
-        if constexpr (sizeof(T) == 2) {
+        if (p.kind == GEMM_PP) {
             hipLaunchKernelGGL((conv_gemm_pp_kernel<T>), grid, block, 0, s, x, w, y, z, g, ep);
             return 0;
         }
-        return -2;
-    }
-    if (p.kind == GEMM_PPRS || p.kind == GEMM_RS) {
-        if constexpr (sizeof(T) == 2) {
+        if (p.kind == GEMM_PPRS || p.kind == GEMM_RS) {
             // LDS-DMA pieces through buffer descriptors (et_bufdma16) unless an operand reaches 2^31 bytes (bit 31 of a lane's offset means
             // "out of range") or ET_CONV_BUF_DMA=0 asks for the flat-address twins.  On the step: -0.4 ms in 20- and 100-step runs
             // (profiles/r06_buffer_dma_default_ab.txt).  (The arm was withdrawn for a day of this round: conv_gemm_rs_kernel<128, 64> produced
@@ -3360,112 +3372,53 @@ static int launch_gemm(const void* X, const void* W, void* Y, const void* zero16
             // property of the addressing form: et_device.h et_wait_vmem_le_lds_read_done, profiles/r06_lds_ring_war_race.txt.)
             const size_t xb = ((size_t)g.N * g.IH * g.IW * g.ldx + (size_t)g.IW * g.ldx) * sizeof(T), wb = (size_t)g.Cout * g.TT * g.Cin * sizeof(T);
             const bool buf = env_int("ET_CONV_BUF_DMA", 1) && xb < (1ull << 31) && wb < (1ull << 31);
-            if (p.kind == GEMM_PPRS) {
-                if (buf) hipLaunchKernelGGL((conv_gemm_pprs_kernel<T>), grid, block, 0, s, x, w, y, z, g, ep);
-                else hipLaunchKernelGGL((conv_gemm_pprs_flat_kernel<T>), grid, block, 0, s, x, w, y, z, g, ep);
-            } else if (p.BN == 128) {
-                if (buf) hipLaunchKernelGGL((conv_gemm_rs_kernel<T, 128, 128, 2, 2>), grid, block, 0, s, x, w, y, z, g, ep);
-                else hipLaunchKernelGGL((conv_gemm_rs_flat_kernel<T, 128, 128, 2, 2>), grid, block, 0, s, x, w, y, z, g, ep);
-            } else {
-                if (buf) hipLaunchKernelGGL((conv_gemm_rs_kernel<T, 128, 64, 2, 2>), grid, block, 0, s, x, w, y, z, g, ep);
-                else hipLaunchKernelGGL((conv_gemm_rs_flat_kernel<T, 128, 64, 2, 2>), grid, block, 0, s, x, w, y, z, g, ep);
-            }
-            return 0;
-        }
-        return -2;
-    }
-    if (p.kind == GEMM_GLDS) {
-        if constexpr (sizeof(T) == 2) {
-            switch (key) {
-                case 12812843: ET_GLDS(128, 128, 2, 2, 4, 3, true); return 0;     // short-K: 32-wide chunks, 3-deep ring
-                case 12806443: ET_GLDS(128, 64, 2, 2, 4, 3, true); return 0;
-                default: break;
-            }
-        }
-        switch (p.BN * 100 + p.BKV * 10 + (p.utap ? 1 : 0)) {
-            case 12881: ET_GLDS(128, 128, 2, 2, 8, 2, true); return 0;
-            case 6481: ET_GLDS(128, 64, 2, 2, 8, 2, true); return 0;
-            case 12841: ET_GLDS(128, 128, 2, 2, 4, 2, true); return 0;
-            case 6441: ET_GLDS(128, 64, 2, 2, 4, 2, true); return 0;
-            case 12840: ET_GLDS(128, 128, 2, 2, 4, 2, false); return 0;
-            case 6440: ET_GLDS(128, 64, 2, 2, 4, 2, false); return 0;
-            default: return -2;
+            if (p.kind == GEMM_PPRS) ET_TWINS(buf, grid, (conv_gemm_pprs_kernel<T>), (conv_gemm_pprs_flat_kernel<T>))
+#define ET_RS(BM_, BN_, WM_, WN_) \
+    if (pp == &rs_rows[i++]) ET_TWINS(buf, grid, (conv_gemm_rs_kernel<T, BM_, BN_, WM_, WN_>), (conv_gemm_rs_flat_kernel<T, BM_, BN_, WM_, WN_>))
+            ET_RS_ROWS
+#undef ET_RS
         }
     }
-    switch (p.BN * 100 + p.BKV * 10 + (p.utap ? 1 : 0)) {
-        case 12881: ET_REG(128, 8, true); return 0;
-        case 6481: ET_REG(64, 8, true); return 0;
-        case 12841: ET_REG(128, 4, true); return 0;
-        case 6441: ET_REG(64, 4, true); return 0;
-        case 12840: ET_REG(128, 4, false); return 0;
-        case 6440: ET_REG(64, 4, false); return 0;
-        default: return -2;
-    }
-#undef ET_GLDS
-#undef ET_REG
+#undef ET_TWINS
+    return -2;
 }
 
 extern "C" int et_conv2d_stats_rows(int N, int OH, int OW) { return (N * OH * OW + 63) / 64; }
 
-extern "C" int et_conv2d_stats_rows_for(int op, int dtype, int N, int IH, int IW, int Cin, int Cout, int KH, int KW, int stride, int pad,
-                                        int have_zero_page) {
-    // rows of the partial-statistics buffer the kernel selected for this problem writes: op 0 = stats_partial of et_conv2d_fwd,
-    // op 1 = bn_stats_partial of et_conv2d_dgrad_bn (stride 1), op 2 = stats_partial of an et_conv2d_fwd call that ALSO passes a
-    // residual (launch_gemm then selects the full-epilogue plan, whose persistent 1x1 form has another tile height and grid: asking
-    // with op 0 for such a call used to return the plain plan's row count -- ADVICE r04).  Arguments of the FORWARD conv.  One row
-    // per 64 output pixels for the tiled kernels; the persistent 1x1 kernel writes one row per (workgroup, row group).
-    if (KH * KW > CONV_MAX_TAPS || stride < 1 || N <= 0 || op < 0 || op > 2) return -2;
-    const bool fwd_full = op == 2;
-    if (fwd_full) op = 0;
-    const int eb = dtype == ET_F32 ? 4 : 2, vec = dtype == ET_F32 ? 4 : 8;
-    GatherGeom g;
-    int rc;
-    if (op == 0) {
-        if (!fwd_full && try_launch_stem(nullptr, nullptr, nullptr, dtype, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout, nullptr, nullptr, 0, nullptr,
-                                         nullptr, 0, have_zero_page ? (const void*)&g : nullptr, nullptr, false)) {
-            const int OH = (IH + 2 * pad - KH) / stride + 1, OW = (IW + 2 * pad - KW) / stride + 1;
-            return (N * OH * OW + 63) / 64;
-        }
-        rc = fwd_geom(g, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout, vec);
-    } else {
-        if (stride != 1) return -2;
-        rc = dgrad_geom(g, 0, 0, N, IH, IW, Cin, Cin, Cout, KH, KW, 1, pad, Cout, vec);
-    }
-    if (rc) return rc < 0 ? rc : -2;
-    const GemmPlan p = plan_gemm(g, eb, have_zero_page != 0, op == 1 || fwd_full);
-    if (p.kind == GEMM_S1) return s1_grid((g.M + p.BM - 1) / p.BM, p) * p.WM;
-    return (g.M + 63) / 64;
+// ---- the stem: shape gate, persistent grid, tile fields -----------------------------------------------------------------------
+static bool stem_eligible(int dtype, int Cin, int Cout, int KH, int KW, int stride, int pad, bool has_residual, bool has_zero_page) {
+    return (dtype == ET_BF16 || dtype == ET_F16) && KH == 6 && KW == 6 && stride == 2 && pad == 2 && Cin == 8 && Cout <= 64 && Cout % 8 == 0 &&
+           !has_residual && has_zero_page;
 }
-
-extern "C" int et_conv2d_stats_adds_for(int op, int dtype, int N, int IH, int IW, int Cin, int Cout, int KH, int KW, int stride, int pad,
-                                        int have_zero_page) {
-    // fp32 atomic additions PER CHANNEL (all shards together) of the same call with a SHARDED accumulator (stats_ld > 0): every
-    // kernel adds once per workgroup that covers the channel -- the persistent kernels (stem, 1x1 stream) once per resident
-    // workgroup, the tiled kernels once per row tile (conv_stats_add_sharded_wg).  adds / ET_BN_SHARDS of them meet on one address.
-    if (KH * KW > CONV_MAX_TAPS || stride < 1 || N <= 0 || op < 0 || op > 2) return -2;
-    const bool fwd_full = op == 2;
-    if (fwd_full) op = 0;
-    const int eb = dtype == ET_F32 ? 4 : 2, vec = dtype == ET_F32 ? 4 : 8;
-    GatherGeom g;
-    int rc;
-    if (op == 0) {
-        if (!fwd_full && try_launch_stem(nullptr, nullptr, nullptr, dtype, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout, nullptr, nullptr, 0, nullptr,
-                                         nullptr, 0, have_zero_page ? (const void*)&g : nullptr, nullptr, false)) {
-            const int OH = (IH + 2 * pad - KH) / stride + 1, OW = (IW + 2 * pad - KW) / stride + 1;
-            const int ntiles = N * ((OH + STEM_TR - 1) / STEM_TR) * ((OW + STEM_TC - 1) / STEM_TC);
-            int grid = env_int("ET_CONV_STEM_WGS", 2 * device_cus());
-            if (grid < 1) grid = 1;
-            return grid < ntiles ? grid : ntiles;
-        }
-        rc = fwd_geom(g, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout, vec);
-    } else {
-        if (stride != 1) return -2;
-        rc = dgrad_geom(g, 0, 0, N, IH, IW, Cin, Cin, Cout, KH, KW, 1, pad, Cout, vec);
-    }
-    if (rc) return rc < 0 ? rc : -2;
-    const GemmPlan p = plan_gemm(g, eb, have_zero_page != 0, op == 1 || fwd_full);
-    if (p.kind == GEMM_S1) return s1_grid((g.M + p.BM - 1) / p.BM, p);
-    return (g.M + p.BM - 1) / p.BM;
+// the stem kernels are persistent (ET_CONV_STEM_WGS: tests shrink the grid to exercise the tile loop; read per launch)
+static int stem_grid(int ntiles) {
+    int grid = env_int("ET_CONV_STEM_WGS", 2 * device_cus());
+    if (grid < 1) grid = 1;
+    return grid < ntiles ? grid : ntiles;
+}
+// image and tile fields of StemArgs / StemWgradArgs (6x6, stride 2, pad 2)
+template <typename A>
+static void stem_tiles(A& a, int N, int IH, int IW) {
+    a.N = N; a.IH = IH; a.IW = IW;
+    a.OH = (IH + 4 - 6) / 2 + 1; a.OW = (IW + 4 - 6) / 2 + 1;
+    a.trn = (a.OH + STEM_TR - 1) / STEM_TR; a.tcn = (a.OW + STEM_TC - 1) / STEM_TC;
+    a.ntiles = N * a.trn * a.tcn;
+}
+// epilogue fields and launch of conv_stem_kernel / conv_stem_u8_kernel (U8); the caller has filled the operands and stem_tiles
+template <bool U8>
+static void launch_stem(StemArgs& a, int dtype, const float* scale, const float* bias, int act, float* stats, int stats_ld, hipStream_t s) {
+    a.scale = scale; a.bias = bias; a.act = act; a.stats = stats; a.stats_ld = stats ? stats_ld : 0;
+    a.stat_rows = (a.N * a.OH * a.OW + 63) / 64;        // == et_conv2d_stats_rows
+    int grid = stem_grid(a.ntiles);
+    if (stats && !stats_ld && grid > a.stat_rows) grid = a.stat_rows;
+#define ET_STEM(T_, ACT_) \
+    do { \
+        if constexpr (U8) hipLaunchKernelGGL((conv_stem_u8_kernel<T_, ACT_>), dim3(grid), dim3(256), 0, s, a); \
+        else hipLaunchKernelGGL((conv_stem_kernel<T_, ACT_>), dim3(grid), dim3(256), 0, s, a); \
+    } while (0)
+    if (dtype == ET_F16) { if (act == ACT_SILU) ET_STEM(et_f16, ACT_SILU); else if (act == ACT_RELU) ET_STEM(et_f16, ACT_RELU); else ET_STEM(et_f16, ACT_NONE); }
+    else { if (act == ACT_SILU) ET_STEM(uint16_t, ACT_SILU); else if (act == ACT_RELU) ET_STEM(uint16_t, ACT_RELU); else ET_STEM(uint16_t, ACT_NONE); }
+#undef ET_STEM
 }
 
 extern "C" int et_conv2d_fwd(const void* x, const void* w, void* y, int dtype, int N, int IH, int IW, int Cin,
@@ -3474,8 +3427,12 @@ extern "C" int et_conv2d_fwd(const void* x, const void* w, void* y, int dtype, i
                              int stats_ld, const void* zero16, et_stream_t stream) {
     if (!x || !w || !y) return -1;
     if (KH * KW > CONV_MAX_TAPS || stride < 1 || N <= 0 || Cout <= 0 || stats_ld < 0 || (stats_ld && stats_ld < Cout)) return -2;
-    if (try_launch_stem(x, w, y, dtype, N, IH, IW, Cin, ldx, Cout, KH, KW, stride, pad, ldy, scale, bias, act, residual,
-                        stats_partial, stats_ld, zero16, (hipStream_t)stream, true)) {
+    if (stem_eligible(dtype, Cin, Cout, KH, KW, stride, pad, residual != nullptr, zero16 != nullptr)) {
+        StemArgs a;
+        a.x = (const uint16_t*)x; a.w = (const uint16_t*)w; a.y = (uint16_t*)y; a.zero = (const uint16_t*)zero16;
+        a.ldx = ldx; a.Cout = Cout; a.ldy = ldy;
+        stem_tiles(a, N, IH, IW);
+        launch_stem<false>(a, dtype, scale, bias, act, stats_partial, stats_ld, (hipStream_t)stream);
         ET_CHECK_LAUNCH();
         return 0;
     }
@@ -3498,10 +3455,7 @@ extern "C" int et_conv2d_fwd(const void* x, const void* w, void* y, int dtype, i
     }
     Epilogue ep{scale, bias, act, residual, ldr, stats_partial, 0};
     ep.stats_ld = stats_partial ? stats_ld : 0;
-    if (dtype == ET_F32) rc = launch_gemm<float>(x, w, y, zero16, g, ep, (hipStream_t)stream);
-    else if (dtype == ET_BF16) rc = launch_gemm<uint16_t>(x, w, y, zero16, g, ep, (hipStream_t)stream);
-    else if (dtype == ET_F16) rc = launch_gemm<et_f16>(x, w, y, zero16, g, ep, (hipStream_t)stream);
-    else return -2;
+    if (!with_dtype(dtype, [&](auto t) { rc = launch_gemm<typename decltype(t)::type>(x, w, y, zero16, g, ep, (hipStream_t)stream); })) return -2;
     if (rc) return rc;
     ET_CHECK_LAUNCH();
     return 0;
@@ -3549,10 +3503,7 @@ static int conv2d_dgrad_impl(const void* dy, const void* wT, void* dx, int dtype
                 }
                 continue;
             }
-            if (dtype == ET_F32) rc = launch_gemm<float>(dy, wT, dx, zero16, g, ep, (hipStream_t)stream);
-            else if (dtype == ET_BF16) rc = launch_gemm<uint16_t>(dy, wT, dx, zero16, g, ep, (hipStream_t)stream);
-            else if (dtype == ET_F16) rc = launch_gemm<et_f16>(dy, wT, dx, zero16, g, ep, (hipStream_t)stream);
-            else return -2;
+            if (!with_dtype(dtype, [&](auto t) { rc = launch_gemm<typename decltype(t)::type>(dy, wT, dx, zero16, g, ep, (hipStream_t)stream); })) return -2;
             if (rc) return rc;
         }
     ET_CHECK_LAUNCH();
@@ -3585,7 +3536,7 @@ static void wgrad_geom(WgradGeom& g, int N, int IH, int IW, int Cin, int ldx, in
     g.dQW = make_fastdiv(OW); g.dQH = make_fastdiv(OH); g.dCin = make_fastdiv(Cin); g.dW1 = make_fastdiv(OW + 1);
     g.PP = N * OH * (OW + 1);
     g.ident = (KH == 1 && KW == 1 && stride == 1 && pad == 0 && OH == IH && OW == IW) ? 1 : 0;
-    g.buf = 0;                   // set per launch (launch_wgrad_tr): needs the group's pixel strides
+    g.buf = 0;                   // set per launch (launch_wgrad): needs the group's pixel strides
     for (int ky = 0; ky < KH; ++ky)
         for (int kx = 0; kx < KW; ++kx) {
             g.dy[ky * KW + kx] = (signed char)(ky - pad);
@@ -3593,11 +3544,33 @@ static void wgrad_geom(WgradGeom& g, int N, int IH, int IW, int Cin, int ldx, in
         }
 }
 
-struct WgradPlan { bool tr; int bm, bn; bool rs; int rs_stride; };
-static WgradPlan plan_wgrad(const WgradGeom& g, int elem_bytes, bool have_zero_page) {
+// the weight-gradient instantiations, one row list per family as for the gather-GEMMs above (expanded into the WgradRow tables here
+// and into the launches of launch_wgrad)
+//      conv_wgrad_tr_kernel: BM BN WM WN
+#define ET_WG_ROWS \
+    ET_WG(256, 256, 2, 4) ET_WG(256, 128, 4, 2) ET_WG(256, 64, 4, 1) \
+    ET_WG(128, 256, 2, 4) ET_WG(128, 128, 2, 2) ET_WG(128, 64, 2, 2) \
+    ET_WG(64, 256, 1, 4)  ET_WG(64, 128, 2, 2)  ET_WG(64, 64, 2, 2)
+//      conv_wgrad_rs_kernel: BM BNC WM WN STRIDE
+#define ET_WGRS_ROWS ET_WGRS(128, 128, 2, 4, 1) ET_WGRS(64, 64, 2, 2, 1) ET_WGRS(128, 64, 2, 2, 2)
+//      conv_wgrad_kernel (register-staged, 256 threads): BM BN
+#define ET_WGREG_ROWS ET_WGREG(128, 128) ET_WGREG(128, 64) ET_WGREG(64, 128) ET_WGREG(64, 64)
+enum { WGRAD_REG = 0, WGRAD_TR = 1, WGRAD_RS = 2 };
+struct WgradRow { int kind, bm, bn, wm, wn, stride; };
+#define ET_WG(BM_, BN_, WM_, WN_) {WGRAD_TR, BM_, BN_, WM_, WN_, 0},
+#define ET_WGRS(BM_, BN_, WM_, WN_, ST_) {WGRAD_RS, BM_, BN_, WM_, WN_, ST_},
+#define ET_WGREG(BM_, BN_) {WGRAD_REG, BM_, BN_, 2, 2, 0},
+static const WgradRow wg_rows[] = {ET_WG_ROWS};
+static const WgradRow wgrs_rows[] = {ET_WGRS_ROWS};
+static const WgradRow wgreg_rows[] = {ET_WGREG_ROWS};
+#undef ET_WG
+#undef ET_WGRS
+#undef ET_WGREG
+
+static const WgradRow* plan_wgrad(const WgradGeom& g, int elem_bytes, bool have_zero_page) {
     const bool wideN = g.NC > 64;
     const bool tallM = g.Cout > 64;            // Cout <= 64 layers: a 64-row tile wastes no MFMA rows
-    WgradPlan p{false, tallM ? 128 : 64, wideN ? 128 : 64, false, 1};
+    struct { bool tr; int bm, bn; bool rs; int rs_stride; } p{false, tallM ? 128 : 64, wideN ? 128 : 64, false, 1};
     // bf16 + zero page: LDS-DMA staging with transposing LDS reads
     p.tr = elem_bytes == 2 && have_zero_page;
     // 256-wide tiles (8 waves, one workgroup per CU): half the L2->LDS bytes per flop of the 128^2 tile
@@ -3627,70 +3600,26 @@ static WgradPlan plan_wgrad(const WgradGeom& g, int elem_bytes, bool have_zero_p
         (long long)g.N * g.IH * g.IW * (g.ldx > g.ldy ? g.ldx : g.ldy) < (1ll << 31)) {
         p.rs = true; p.rs_stride = 2; p.bm = 128; p.bn = 64;
     }
-    return p;
+    if (p.rs) return find_row(wgrs_rows, [&](const WgradRow& r) { return r.bm == p.bm && r.bn == p.bn && r.stride == p.rs_stride; });
+    const auto tile = [&](const WgradRow& r) { return r.bm == p.bm && r.bn == p.bn; };
+    return p.tr ? find_row(wg_rows, tile) : find_row(wgreg_rows, tile);
 }
-static void wgrad_plan_name(const WgradPlan& p, int dtype, char* buf, int n) {
+static void wgrad_plan_name(const WgradRow& p, int dtype, char* buf, int n) {
     const char* t = dtype_tname(dtype);
-    if (p.rs) {
-        if (p.rs_stride == 2) snprintf(buf, n, "conv_wgrad_rs_kernel<%s, %d, %d, %d, %d, 2>", t, p.bm, p.bn, 2, 2);
-        else snprintf(buf, n, "conv_wgrad_rs_kernel<%s, %d, %d, %d, %d>", t, p.bm, p.bn, 2, p.bm == 128 ? 4 : 2);
-    } else if (p.tr) {
-        const int wm = p.bm == 256 ? (p.bn == 256 ? 2 : 4) : (p.bm == 128 ? 2 : (p.bn == 256 ? 1 : 2));
-        const int wn = p.bm == 256 ? (p.bn == 256 ? 4 : (p.bn == 128 ? 2 : 1)) : (p.bn == 256 ? 4 : 2);
-        snprintf(buf, n, "conv_wgrad_tr_kernel<%s, %d, %d, %d, %d>", t, p.bm, p.bn, wm, wn);
-    } else {
-        snprintf(buf, n, "conv_wgrad_kernel<%s, %d, %d>", t, p.bm > 64 ? 128 : 64, p.bn > 64 ? 128 : 64);
-    }
+    if (p.kind == WGRAD_RS && p.stride == 2) snprintf(buf, n, "conv_wgrad_rs_kernel<%s, %d, %d, %d, %d, 2>", t, p.bm, p.bn, p.wm, p.wn);   // a default argument is not printed
+    else if (p.kind == WGRAD_RS) snprintf(buf, n, "conv_wgrad_rs_kernel<%s, %d, %d, %d, %d>", t, p.bm, p.bn, p.wm, p.wn);
+    else if (p.kind == WGRAD_TR) snprintf(buf, n, "conv_wgrad_tr_kernel<%s, %d, %d, %d, %d>", t, p.bm, p.bn, p.wm, p.wn);
+    else snprintf(buf, n, "conv_wgrad_kernel<%s, %d, %d>", t, p.bm, p.bn);
 }
 
-template <typename T>
-static void launch_wgrad(const WgradGroup& grp, const void* zero16, WgradGeom& g, hipStream_t s) {
-    constexpr int VEC = et_elem<T>::VEC;
-    constexpr int BKP = 8 * VEC;
-    const WgradPlan wp = plan_wgrad(g, (int)sizeof(T), zero16 != nullptr);
-    const bool tr = wp.tr, wideN = g.NC > 64, tallM = g.Cout > 64;
-    const int bm = wp.bm, bn = wp.bn;
-    if (wp.rs) {
-        if constexpr (sizeof(T) == 2) {
-            // same split policy as below, over the padded raster: one round of co-resident workgroups, >= ~25 chunks each
-            const int nci = (g.Cin + bn - 1) / bn;
-            g.ntn = 3 * nci; g.ntm = (g.Cout + bm - 1) / bm;
-            const int tiles = grp.n * g.ntn * g.ntm;
-            const int n_cu = device_cus();
-            // stride 1: 68 KB / 34 KB of LDS, 8 / 4 waves, <= 128 VGPRs; stride 2: 67 KB (4 waves)
-            const int slots = wp.rs_stride == 2 ? 2 : (bm == 128 ? 2 : 4);
-            const int cap = slots * n_cu;
-            const int max_sk = max(1, g.PP / (64 * 25));
-            auto eff = [&](int k) { const int b = tiles * k; return (double)b / ((double)((b + cap - 1) / cap) * cap); };
-            int sk = max(1, min(cap / tiles, max_sk));
-            if (eff(sk) < 0.8)
-                for (int k = sk + 1; k <= min(max_sk, max(4, 2 * cap / tiles)); ++k)
-                    if (eff(k) > eff(sk) + 0.1) sk = k;
-            sk = max(1, min(sk, max_sk));
-            int per = (g.PP + sk - 1) / sk;
-            per = ((per + 63) / 64) * 64;
-            sk = (g.PP + per - 1) / per;
-            g.xcd = 1; g.Pper = per; g.nsk = sk;
-            const dim3 grid(grp.n * g.ntn * g.ntm * sk);
-            const uint16_t* z = (const uint16_t*)zero16;
-            if (wp.rs_stride == 2) hipLaunchKernelGGL((conv_wgrad_rs_kernel<T, 128, 64, 2, 2, 2>), grid, dim3(256), 0, s, grp, z, g);
-            else if (bm == 128) hipLaunchKernelGGL((conv_wgrad_rs_kernel<T, 128, 128, 2, 4>), grid, dim3(512), 0, s, grp, z, g);
-            else hipLaunchKernelGGL((conv_wgrad_rs_kernel<T, 64, 64, 2, 2>), grid, dim3(256), 0, s, grp, z, g);
-            return;
-        }
-    }
-    const int tiles = grp.n * ((g.NC + bn - 1) / bn) * ((g.Cout + bm - 1) / bm);   // the whole group shares the split
-    // Split K so that the grid is a whole number of residency rounds: `slots` workgroups of this tile fit on
-    // a CU (LDS- or register-limited), so up to slots*CUs run at once and a grid a little OVER a multiple of
-    // that costs a whole extra round (e.g. 36 tiles x 29 splits = 1044 workgroups on 1024 slots).  Fewer
-    // splits also mean fewer fp32 atomics on dW.
-    const int n_cu = device_cus();
-    const int lds_kb = tr ? (bm + bn) / 4 : 64;                // 2 stages x 64 pixels x (bm+bn) channels x 2 B
-    int slots = tr ? max(1, min(160 / lds_kb, bm * bn <= 64 * 64 ? 5 : (bm * bn <= 128 * 64 ? 3 : 2))) : 2;
-    // measured: ONE full round of co-resident workgroups with >= ~25 chunks (1600 pixels) each beats two
-    // shorter rounds (prologue, first-chunk latency and the atomic epilogue are per workgroup)
-    const int cap = slots * n_cu;
-    const int max_sk = max(1, g.P / (BKP * 25));
+// Split K so that the grid is a whole number of residency rounds: up to cap (= workgroups per CU x CUs) workgroups run at once,
+// and a grid a little OVER a multiple of that costs a whole extra round (e.g. 36 tiles x 29 splits = 1044 workgroups on 1024
+// slots).  Fewer splits also mean fewer fp32 atomics on dW.  Measured: ONE full round of co-resident workgroups with >= ~25 chunks
+// (1600 pixels) each beats two shorter rounds (prologue, first-chunk latency and the atomic epilogue are per workgroup).
+// len = the reduction length (pixels / padded slots), chunk = the kernel's K-chunk; per = slice length, a multiple of chunk.
+struct SplitK { int per, nsk; };
+static SplitK wgrad_split_k(int len, int chunk, int tiles, int cap) {
+    const int max_sk = max(1, len / (chunk * 25));
     auto eff = [&](int k) { const int b = tiles * k; return (double)b / ((double)((b + cap - 1) / cap) * cap); };
     int sk = max(1, min(cap / tiles, max_sk));
     // grids that cannot fill one round evenly: take the split (a few rounds at most) that wastes least
@@ -3698,43 +3627,72 @@ static void launch_wgrad(const WgradGroup& grp, const void* zero16, WgradGeom& g
         for (int k = sk + 1; k <= min(max_sk, max(4, 2 * cap / tiles)); ++k)
             if (eff(k) > eff(sk) + 0.1) sk = k;
     sk = max(1, min(sk, max_sk));
-    int per = (g.P + sk - 1) / sk;
-    per = ((per + BKP - 1) / BKP) * BKP;
-    sk = (g.P + per - 1) / per;
+    int per = (len + sk - 1) / sk;
+    per = ((per + chunk - 1) / chunk) * chunk;
+    return SplitK{per, (len + per - 1) / per};
+}
+
+template <typename T>
+static int launch_wgrad(const WgradGroup& grp, const void* zero16, WgradGeom& g, hipStream_t s) {
+    constexpr int VEC = et_elem<T>::VEC;
+    constexpr int BKP = 8 * VEC;
+    const WgradRow* const wp = plan_wgrad(g, (int)sizeof(T), zero16 != nullptr);
+    if (!wp) return -2;
+    const bool tr = wp->kind == WGRAD_TR;
+    const int bm = wp->bm, bn = wp->bn, n_cu = device_cus();
+    const uint16_t* z = (const uint16_t*)zero16;
     g.xcd = 1;                                     // the K-splits of one dW tile share an XCD (a knob until r02: always on)
-    g.Pper = per;
-    g.ntn = (g.NC + bn - 1) / bn; g.ntm = (g.Cout + bm - 1) / bm; g.nsk = sk;
-    const dim3 block(256);
+    g.ntm = (g.Cout + bm - 1) / bm;
+    int i = 0;                                     // the row lists as launches: expansion i instantiates row i of the family's table
+    if constexpr (sizeof(T) == 2) {
+        if (wp->kind == WGRAD_RS) {
+            // the split policy over the padded raster, in 64-slot chunks
+            g.ntn = 3 * ((g.Cin + bn - 1) / bn);
+            // stride 1: 68 KB / 34 KB of LDS, 8 / 4 waves, <= 128 VGPRs; stride 2: 67 KB (4 waves)
+            const int slots = wp->stride == 2 ? 2 : (bm == 128 ? 2 : 4);
+            const SplitK sk = wgrad_split_k(g.PP, 64, grp.n * g.ntn * g.ntm, slots * n_cu);
+            g.Pper = sk.per; g.nsk = sk.nsk;
+            const dim3 grid(grp.n * g.ntn * g.ntm * sk.nsk);
+#define ET_WGRS(BM_, BN_, WM_, WN_, ST_) \
+    if (wp == &wgrs_rows[i++]) { hipLaunchKernelGGL((conv_wgrad_rs_kernel<T, BM_, BN_, WM_, WN_, ST_>), grid, dim3(64 * WM_ * WN_), 0, s, grp, z, g); return 0; }
+            ET_WGRS_ROWS
+#undef ET_WGRS
+            return -2;
+        }
+    }
+    g.ntn = (g.NC + bn - 1) / bn;
+    // `slots` workgroups of this tile fit on a CU (LDS- or register-limited); the whole group shares the split
+    const int lds_kb = tr ? (bm + bn) / 4 : 64;                // 2 stages x 64 pixels x (bm+bn) channels x 2 B
+    const int slots = tr ? max(1, min(160 / lds_kb, bm * bn <= 64 * 64 ? 5 : (bm * bn <= 128 * 64 ? 3 : 2))) : 2;
+    const SplitK sk = wgrad_split_k(g.P, BKP, grp.n * g.ntn * g.ntm, slots * n_cu);
+    g.Pper = sk.per; g.nsk = sk.nsk;
     if constexpr (sizeof(T) == 2) {
         if (tr) {
-            const dim3 grid(grp.n * g.ntn * g.ntm * sk);
-            const uint16_t* z = (const uint16_t*)zero16;
+            const dim3 grid(grp.n * g.ntn * g.ntm * sk.nsk);
             // 1x1 stride-1 layers: buffer-descriptor pieces when every tensor of the group spans < 2^31 bytes (conv_wgrad_tr_kernel, g.buf)
             g.buf = g.ident && env_int("ET_CONV_BUF_DMA", 1);
-            for (int i = 0; i < grp.n && g.buf; ++i)
-                if ((size_t)g.P * grp.it[i].ldx * 2 >= (1ull << 31) || (size_t)g.P * grp.it[i].ldy * 2 >= (1ull << 31)) g.buf = 0;
-#define ET_WG(BM_, BN_, WM_, WN_) hipLaunchKernelGGL((conv_wgrad_tr_kernel<T, BM_, BN_, WM_, WN_>), grid, dim3(64 * WM_ * WN_), 0, s, grp, z, g)
-            if (bm == 256) { if (bn == 256) ET_WG(256, 256, 2, 4); else if (bn == 128) ET_WG(256, 128, 4, 2); else ET_WG(256, 64, 4, 1); }
-            else if (bm == 128) { if (bn == 256) ET_WG(128, 256, 2, 4); else if (bn == 128) ET_WG(128, 128, 2, 2); else ET_WG(128, 64, 2, 2); }
-            else { if (bn == 256) ET_WG(64, 256, 1, 4); else if (bn == 128) ET_WG(64, 128, 2, 2); else ET_WG(64, 64, 2, 2); }
+            for (int k = 0; k < grp.n && g.buf; ++k)
+                if ((size_t)g.P * grp.it[k].ldx * 2 >= (1ull << 31) || (size_t)g.P * grp.it[k].ldy * 2 >= (1ull << 31)) g.buf = 0;
+#define ET_WG(BM_, BN_, WM_, WN_) \
+    if (wp == &wg_rows[i++]) { hipLaunchKernelGGL((conv_wgrad_tr_kernel<T, BM_, BN_, WM_, WN_>), grid, dim3(64 * WM_ * WN_), 0, s, grp, z, g); return 0; }
+            ET_WG_ROWS
 #undef ET_WG
-            return;
+            return -2;
         }
     }
     // register-staged kernel (fp32 parity mode, callers without a zero page): one launch per item
-    const dim3 grid(g.ntn * g.ntm * sk);
-    for (int i = 0; i < grp.n; ++i) {
-        const T* xx = (const T*)grp.it[i].x; const T* yy = (const T*)grp.it[i].dy;
-        float* dw = grp.it[i].dw;
-        g.ldx = grp.it[i].ldx; g.ldy = grp.it[i].ldy;
-        if (tallM) {
-            if (wideN) hipLaunchKernelGGL((conv_wgrad_kernel<T, 128, 128>), grid, block, 0, s, xx, yy, dw, g);
-            else hipLaunchKernelGGL((conv_wgrad_kernel<T, 128, 64>), grid, block, 0, s, xx, yy, dw, g);
-        } else {
-            if (wideN) hipLaunchKernelGGL((conv_wgrad_kernel<T, 64, 128>), grid, block, 0, s, xx, yy, dw, g);
-            else hipLaunchKernelGGL((conv_wgrad_kernel<T, 64, 64>), grid, block, 0, s, xx, yy, dw, g);
-        }
+    const dim3 grid(g.ntn * g.ntm * sk.nsk), block(256);
+    for (int k = 0; k < grp.n; ++k) {
+        const T* xx = (const T*)grp.it[k].x; const T* yy = (const T*)grp.it[k].dy;
+        float* dw = grp.it[k].dw;
+        g.ldx = grp.it[k].ldx; g.ldy = grp.it[k].ldy;
+        i = 0;
+#define ET_WGREG(BM_, BN_) \
+    if (wp == &wgreg_rows[i++]) hipLaunchKernelGGL((conv_wgrad_kernel<T, BM_, BN_>), grid, block, 0, s, xx, yy, dw, g);
+        ET_WGREG_ROWS
+#undef ET_WGREG
     }
+    return wp->kind == WGRAD_REG ? 0 : -2;
 }
 
 extern "C" int et_conv2d_wgrad_grouped(const et_wgrad_item* items, int n_items, int dtype, int N, int IH, int IW, int Cin,
@@ -3756,10 +3714,9 @@ extern "C" int et_conv2d_wgrad_grouped(const et_wgrad_item* items, int n_items, 
     WgradGeom g;
     wgrad_geom(g, N, IH, IW, Cin, items[0].ldx, Cout, KH, KW, stride, pad, items[0].ldy);
     if (g.P <= 0) return 0;
-    if (dtype == ET_F32) launch_wgrad<float>(grp, zero16, g, (hipStream_t)stream);
-    else if (dtype == ET_BF16) launch_wgrad<uint16_t>(grp, zero16, g, (hipStream_t)stream);
-    else if (dtype == ET_F16) launch_wgrad<et_f16>(grp, zero16, g, (hipStream_t)stream);
-    else return -2;
+    int rc = 0;
+    if (!with_dtype(dtype, [&](auto t) { rc = launch_wgrad<typename decltype(t)::type>(grp, zero16, g, (hipStream_t)stream); })) return -2;
+    if (rc) return rc;
     ET_CHECK_LAUNCH();
     return 0;
 }
@@ -3864,26 +3821,10 @@ extern "C" int et_conv2d_stem_u8_fwd(const void* const* seg_ptrs, const int* seg
     a.norm = norm_scale;
     a.x = nullptr; a.zero = (const uint16_t*)zero16;      // the weight rows beyond Cout still come from the zero page
     a.w = (const uint16_t*)w; a.y = (uint16_t*)y;
-    a.N = N; a.IH = IH; a.IW = IW; a.ldx = 8; a.Cout = Cout; a.ldy = ldy;
-    a.OH = (IH + 4 - 6) / 2 + 1; a.OW = (IW + 4 - 6) / 2 + 1;
+    a.ldx = 8; a.Cout = Cout; a.ldy = ldy;
+    stem_tiles(a, N, IH, IW);
     if (a.OH < 1 || a.OW < 1) return -2;
-    a.trn = (a.OH + STEM_TR - 1) / STEM_TR; a.tcn = (a.OW + STEM_TC - 1) / STEM_TC;
-    a.ntiles = N * a.trn * a.tcn;
-    a.scale = scale; a.bias = bias; a.act = act; a.stats = stats; a.stats_ld = stats ? stats_ld : 0;
-    a.stat_rows = (N * a.OH * a.OW + 63) / 64;
-    int grid = env_int("ET_CONV_STEM_WGS", 2 * device_cus());
-    if (grid < 1) grid = 1;
-    if (grid > a.ntiles) grid = a.ntiles;
-    if (stats && !stats_ld && grid > a.stat_rows) grid = a.stat_rows;
-    hipStream_t s = (hipStream_t)stream;
-#define ET_STEM(T_) \
-    do { \
-        if (act == ACT_SILU) hipLaunchKernelGGL((conv_stem_u8_kernel<T_, ACT_SILU>), dim3(grid), dim3(256), 0, s, a); \
-        else if (act == ACT_RELU) hipLaunchKernelGGL((conv_stem_u8_kernel<T_, ACT_RELU>), dim3(grid), dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL((conv_stem_u8_kernel<T_, ACT_NONE>), dim3(grid), dim3(256), 0, s, a); \
-    } while (0)
-    if (dtype == ET_F16) ET_STEM(et_f16); else ET_STEM(uint16_t);
-#undef ET_STEM
+    launch_stem<true>(a, dtype, scale, bias, act, stats, stats_ld, (hipStream_t)stream);
     ET_CHECK_LAUNCH();
     return 0;
 }
@@ -3896,14 +3837,10 @@ extern "C" int et_conv2d_stem_u8_wgrad(const void* const* seg_ptrs, const int* s
     if (N < 0) return N;
     a.norm = norm_scale;
     a.dy = (const uint16_t*)dy; a.zero = (const uint16_t*)zero16; a.dw = dw;
-    a.N = N; a.IH = IH; a.IW = IW; a.ldy = ldy; a.Cout = Cout;
-    a.OH = (IH + 4 - 6) / 2 + 1; a.OW = (IW + 4 - 6) / 2 + 1;
+    a.ldy = ldy; a.Cout = Cout;
+    stem_tiles(a, N, IH, IW);
     if (a.OH < 1 || a.OW < 1) return -2;
-    a.trn = (a.OH + STEM_TR - 1) / STEM_TR; a.tcn = (a.OW + STEM_TC - 1) / STEM_TC;
-    a.ntiles = N * a.trn * a.tcn;
-    int grid = env_int("ET_CONV_STEM_WGS", 2 * device_cus());
-    if (grid < 1) grid = 1;
-    if (grid > a.ntiles) grid = a.ntiles;
+    const int grid = stem_grid(a.ntiles);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == ET_F16) hipLaunchKernelGGL((conv_stem_u8_wgrad_kernel<et_f16>), dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((conv_stem_u8_wgrad_kernel<uint16_t>), dim3(grid), dim3(256), 0, s, a);
@@ -3912,6 +3849,43 @@ extern "C" int et_conv2d_stem_u8_wgrad(const void* const* seg_ptrs, const int* s
 }
 
 // ---- introspection (tests, bench.py) -----------------------------------------------------------------------
+// What the entry points launch for a problem, found through the functions they call themselves (stem_eligible, fwd_geom /
+// dgrad_geom / wgrad_geom, plan_gemm / plan_wgrad).  op as et_conv2d_kernel_name numbers it; arguments of the FORWARD conv.
+struct ConvChoice {
+    enum { STEM, GEMM, WGRAD } kind;
+    int stem_pixels, stem_ntiles;                // STEM: output pixels, tiles
+    GatherGeom g; const GemmPlan* gemm;          // GEMM
+    const WgradRow* wgrad;                       // WGRAD
+};
+static int resolve_conv(ConvChoice& c, int op, int dtype, int N, int IH, int IW, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                        bool have_zero_page, int parity_class) {
+    if (KH * KW > CONV_MAX_TAPS || stride < 1 || N <= 0 || op < 0 || op > 4) return -2;
+    const int eb = dtype == ET_F32 ? 4 : 2, vec = dtype == ET_F32 ? 4 : 8;
+    if (op == 2) {
+        WgradGeom g;
+        wgrad_geom(g, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout);
+        c.kind = ConvChoice::WGRAD; c.wgrad = plan_wgrad(g, eb, have_zero_page);
+        return c.wgrad ? 0 : -2;
+    }
+    const bool full = op >= 3;
+    if (op == 0 || op == 4) {
+        if (stem_eligible(dtype, Cin, Cout, KH, KW, stride, pad, full, have_zero_page)) {
+            StemArgs a;
+            stem_tiles(a, N, IH, IW);
+            c.kind = ConvChoice::STEM; c.stem_pixels = N * a.OH * a.OW; c.stem_ntiles = a.ntiles;
+            return 0;
+        }
+        if (fwd_geom(c.g, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout, vec)) return -2;
+    } else {
+        if (stride > 2) return -2;
+        const int py = parity_class / stride, px = parity_class % stride;
+        if (py >= stride) return -2;
+        if (dgrad_geom(c.g, py, px, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout, vec)) return -2;
+    }
+    c.kind = ConvChoice::GEMM; c.gemm = plan_gemm(c.g, eb, have_zero_page, full);
+    return c.gemm ? 0 : -2;
+}
+
 extern "C" int et_conv2d_kernel_name(int op, int dtype, int N, int IH, int IW, int Cin, int Cout, int KH, int KW, int stride,
                                      int pad, int have_zero_page, int parity_class, char* buf, int buflen) {
     // op 0 = forward, 1 = dgrad (stride 2: parity_class 0..3 selects one of its four launches), 2 = wgrad, 3 = dgrad whose epilogue
@@ -3920,33 +3894,48 @@ extern "C" int et_conv2d_kernel_name(int op, int dtype, int N, int IH, int IW, i
     // Arguments as for et_conv2d_fwd (Cin/Cout of the FORWARD conv).  Writes the name of the kernel instantiation the
     // corresponding entry point launches, spelled as rocprofv3 prints it.  Host only; launches nothing.
     if (!buf || buflen < 8) return -1;
-    if (KH * KW > CONV_MAX_TAPS || stride < 1 || N <= 0) return -2;
-    const int eb = dtype == ET_F32 ? 4 : 2, vec = dtype == ET_F32 ? 4 : 8;
-    if (op == 2) {
-        WgradGeom g;
-        wgrad_geom(g, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout);
-        wgrad_plan_name(plan_wgrad(g, eb, have_zero_page != 0), dtype, buf, buflen);
-        return 0;
-    }
-    GatherGeom g;
-    const bool full = op == 3 || op == 4;
-    if (op == 3) op = 1;
-    if (op == 4) op = 0;
-    if (op == 0) {
-        if (!full && try_launch_stem(nullptr, nullptr, nullptr, dtype, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout, nullptr, nullptr, 0,
-                                     nullptr, nullptr, 0, have_zero_page ? (const void*)buf : nullptr, nullptr, false)) {
-            snprintf(buf, buflen, "conv_stem_kernel");       // rocprofv3: "void conv_stem_kernel<ACT>(StemArgs)"
-            return 0;
-        }
-        if (fwd_geom(g, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout, vec)) return -2;
-    } else if (op == 1) {
-        if (stride > 2 || Cout % vec) return -2;
-        const int py = parity_class / stride, px = parity_class % stride;
-        if (py >= stride) return -2;
-        if (dgrad_geom(g, py, px, N, IH, IW, Cin, Cin, Cout, KH, KW, stride, pad, Cout, vec)) return -2;
-    } else return -2;
-    plan_name(plan_gemm(g, eb, have_zero_page != 0, full), dtype, buf, buflen);
+    ConvChoice c;
+    const int rc = resolve_conv(c, op, dtype, N, IH, IW, Cin, Cout, KH, KW, stride, pad, have_zero_page != 0, parity_class);
+    if (rc) return rc;
+    if (c.kind == ConvChoice::STEM) snprintf(buf, buflen, "conv_stem_kernel");       // rocprofv3: "void conv_stem_kernel<ACT>(StemArgs)"
+    else if (c.kind == ConvChoice::WGRAD) wgrad_plan_name(*c.wgrad, dtype, buf, buflen);
+    else plan_name(*c.gemm, dtype, buf, buflen);
     return 0;
+}
+
+// the statistics entry points number their ops 0 = stats_partial of et_conv2d_fwd, 1 = bn_stats_partial of et_conv2d_dgrad_bn (stride
+// 1), 2 = stats_partial of an et_conv2d_fwd call that ALSO passes a residual (launch_gemm then selects the full-epilogue plan, whose
+// persistent 1x1 form has another tile height and grid: asking with op 0 for such a call used to return the plain plan's row count
+// -- ADVICE r04): resolve_conv's 0, 3 and 4
+static int resolve_stats(ConvChoice& c, int op, int dtype, int N, int IH, int IW, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                         int have_zero_page) {
+    if (op < 0 || op > 2 || (op == 1 && stride != 1)) return -2;
+    return resolve_conv(c, op == 0 ? 0 : (op == 1 ? 3 : 4), dtype, N, IH, IW, Cin, Cout, KH, KW, stride, pad, have_zero_page != 0, 0);
+}
+
+extern "C" int et_conv2d_stats_rows_for(int op, int dtype, int N, int IH, int IW, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                        int have_zero_page) {
+    // rows of the partial-statistics buffer the kernel selected for this problem writes.  Arguments of the FORWARD conv.  One row
+    // per 64 output pixels for the tiled kernels; the persistent 1x1 kernel writes one row per (workgroup, row group).
+    ConvChoice c;
+    const int rc = resolve_stats(c, op, dtype, N, IH, IW, Cin, Cout, KH, KW, stride, pad, have_zero_page);
+    if (rc) return rc;
+    if (c.kind == ConvChoice::STEM) return (c.stem_pixels + 63) / 64;
+    if (c.gemm->kind == GEMM_S1) return s1_grid((c.g.M + c.gemm->BM - 1) / c.gemm->BM, *c.gemm) * c.gemm->WM;
+    return (c.g.M + 63) / 64;
+}
+
+extern "C" int et_conv2d_stats_adds_for(int op, int dtype, int N, int IH, int IW, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                        int have_zero_page) {
+    // fp32 atomic additions PER CHANNEL (all shards together) of the same call with a SHARDED accumulator (stats_ld > 0): every
+    // kernel adds once per workgroup that covers the channel -- the persistent kernels (stem, 1x1 stream) once per resident
+    // workgroup, the tiled kernels once per row tile (conv_stats_add_sharded_wg).  adds / ET_BN_SHARDS of them meet on one address.
+    ConvChoice c;
+    const int rc = resolve_stats(c, op, dtype, N, IH, IW, Cin, Cout, KH, KW, stride, pad, have_zero_page);
+    if (rc) return rc;
+    if (c.kind == ConvChoice::STEM) return stem_grid(c.stem_ntiles);
+    const int ntm = (c.g.M + c.gemm->BM - 1) / c.gemm->BM;
+    return c.gemm->kind == GEMM_S1 ? s1_grid(ntm, *c.gemm) : ntm;
 }
 
 extern "C" int et_conv2d_stem_kernel_name(int op, int dtype, int in_is_u8, int C, int N, int IH, int IW, int Cout, int KH, int KW, int stride,

@@ -201,7 +201,7 @@ def test_conv_wgrad_grouped(hip, dtype):
 # a copy -- so a change of the tile policy that silently drops a kernel out of test coverage fails here.
 GLDS = "conv_gemm_glds_kernel<"
 RS128, RS64 = "conv_gemm_rs_kernel<128, 128, 2, 2>", "conv_gemm_rs_kernel<128, 64, 2, 2>"
-S1 = "conv1x1_stream_kernel<"          # prefix: the shape table behind it (csrc/conv.hip plan_s1) is pinned by test_stream_kernel_shape_table
+S1 = "conv1x1_stream_kernel<"          # prefix: the shape table behind it (csrc/conv.hip ET_S1_ROWS) is pinned by test_stream_kernel_shape_table below
 SELECT = [
     # N, H, W, Cin, Cout, k, s, p, fwd kernel, dgrad kernels (per parity class), wgrad kernel
     ((2, 20, 20, 256, 256, 3, 1, 1), "conv_gemm_pprs_kernel", ["conv_gemm_pprs_kernel"], "conv_wgrad_rs_kernel<128, 128, 2, 4>"),
@@ -305,6 +305,30 @@ def test_kernel_names_carry_the_storage_type(hip):
     assert ops.kernel_name("fwd", torch.float16, 2, 12, 12, 128, 128, 3, 1, 1) == "conv_gemm_rs_kernel<et_f16, 128, 128, 2, 2>"
     assert ops.kernel_name("fwd", torch.bfloat16, 2, 12, 12, 64, 64, 1, 1, 0).startswith("conv1x1_stream_kernel<unsigned short, 1, ")
     assert ops.kernel_name("fwd", torch.float32, 2, 12, 12, 64, 64, 1, 1, 0).startswith("conv_gemm_glds_kernel<float, ")
+
+
+# conv1x1_stream_kernel's instantiations (csrc/conv.hip ET_S1_ROWS): (full epilogue, Cin, Cout) -> KC, WN, TN, WM, TMW, NS, WGS
+STREAM_SHAPES = {
+    (False, 256, 256): (4, 4, 2, 1, 1, 8, 2), (False, 256, 128): (4, 2, 2, 2, 1, 6, 2),
+    (False, 128, 256): (2, 4, 2, 1, 2, 6, 2), (False, 128, 128): (2, 2, 2, 2, 2, 3, 2), (False, 128, 64): (2, 1, 2, 4, 1, 3, 2),
+    (False, 64, 256): (1, 4, 2, 1, 2, 6, 2), (False, 64, 128): (1, 2, 2, 2, 2, 3, 2), (False, 64, 64): (1, 1, 2, 4, 1, 3, 2),
+    (True, 256, 256): (4, 8, 1, 1, 1, 16, 1), (True, 256, 128): (4, 4, 1, 2, 1, 10, 1),
+    (True, 128, 256): (2, 4, 2, 1, 1, 8, 2), (True, 128, 128): (2, 2, 2, 2, 1, 6, 2), (True, 128, 64): (2, 1, 2, 4, 1, 3, 2),
+    (True, 64, 256): (1, 4, 2, 1, 1, 8, 2), (True, 64, 128): (1, 2, 2, 2, 1, 6, 2), (True, 64, 64): (1, 1, 2, 4, 1, 3, 2),
+}
+
+
+def test_stream_kernel_shape_table(hip):
+    """the complete name of every conv1x1_stream_kernel instantiation, as the library reports it for the layer shape that selects it:
+    the name is formatted from the table row that the launch dispatches on, so this pins what runs.  Host logic only."""
+    from efficientteacher_amd import ops
+    assert len(STREAM_SHAPES) == 16
+    for (full, cin, cout), args in STREAM_SHAPES.items():
+        name = ops.kernel_name("fwd_res" if full else "fwd", torch.bfloat16, 1, 8, 8, cin, cout, 1, 1, 0)
+        want = "conv1x1_stream_kernel<unsigned short, " + ", ".join(str(a) for a in args) + (", true>" if full else ", false>")
+        assert name == want, (full, cin, cout)
+    for op in ("fwd", "fwd_res"):           # 256 -> 64: no such row (s1_eligible excludes it)
+        assert not ops.kernel_name(op, torch.bfloat16, 1, 8, 8, 256, 64, 1, 1, 0).startswith(S1)
 
 
 @pytest.mark.parametrize("dma_late,seed", [(1, 3), (0, 5), (1, 11)])
