@@ -3097,6 +3097,14 @@ template <typename F> static bool with_dtype(int dtype, F&& f) {
     return true;
 }
 
+// An NHWC operand of `ch` channels over pixel stride `ld` (nullptr: an optional operand that is absent).  Every kernel family reads and
+// writes it in 16-byte vectors (u32x4 / float4 loads and stores, LDS-DMA, buffer descriptors) at base + pixel * ld + 8-channel
+// group without looking at the address: the channels lie inside the pixel, the pixel stride is whole vectors (`vec` elements of
+// 16 bytes) and the base is 16-byte aligned, or the entry point returns -2 before any launch.
+static bool nhwc_ok(const void* p, int ld, int ch, int vec) {
+    return !p || (ld >= ch && ld % vec == 0 && ((uintptr_t)p & 15) == 0);
+}
+
 static int fill_common(GatherGeom& g, int N, int IH, int IW, int Cin, int ldx, int QH, int QW, int OH, int OW,
                        int Cout, int ldy, int vec) {
     if (Cin % vec) return -2;
@@ -3427,6 +3435,8 @@ extern "C" int et_conv2d_fwd(const void* x, const void* w, void* y, int dtype, i
                              int stats_ld, const void* zero16, et_stream_t stream) {
     if (!x || !w || !y) return -1;
     if (KH * KW > CONV_MAX_TAPS || stride < 1 || N <= 0 || Cout <= 0 || stats_ld < 0 || (stats_ld && stats_ld < Cout)) return -2;
+    const int vec = dtype == ET_F32 ? 4 : 8;
+    if (!nhwc_ok(x, ldx, Cin, vec) || !nhwc_ok(y, ldy, Cout, vec) || !nhwc_ok(residual, ldr, Cout, vec) || ((uintptr_t)w & 15)) return -2;
     if (stem_eligible(dtype, Cin, Cout, KH, KW, stride, pad, residual != nullptr, zero16 != nullptr)) {
         StemArgs a;
         a.x = (const uint16_t*)x; a.w = (const uint16_t*)w; a.y = (uint16_t*)y; a.zero = (const uint16_t*)zero16;
@@ -3437,7 +3447,6 @@ extern "C" int et_conv2d_fwd(const void* x, const void* w, void* y, int dtype, i
         return 0;
     }
     GatherGeom g;
-    const int vec = dtype == ET_F32 ? 4 : 8;
     int rc = fwd_geom(g, N, IH, IW, Cin, ldx, Cout, KH, KW, stride, pad, ldy, vec);
     if (rc) return rc;
     if (residual && !(residual == (const void*)y && ldr == ldy)) {
@@ -3486,6 +3495,8 @@ static int conv2d_dgrad_impl(const void* dy, const void* wT, void* dx, int dtype
     if (residual && stride != 1) return -2;        // the fused shortcut-gradient add is a stride-1 (Bottleneck) feature
     if (bn_y && (stride != 1 || !bn_scale || !bn_shift || !bn_stats || Cin % 8 || bn_stats_ld < 0 || (bn_stats_ld && bn_stats_ld < Cin))) return -2;   // one launch, whole channel groups
     const int vec = dtype == ET_F32 ? 4 : 8;
+    if (!nhwc_ok(dy, ldy, Cout, vec) || !nhwc_ok(dx, ldx, Cin, vec) || !nhwc_ok(residual, ldr, Cin, vec) || !nhwc_ok(bn_y, ld_bn, Cin, vec) ||
+        ((uintptr_t)wT & 15)) return -2;
     for (int py = 0; py < stride; ++py)
         for (int px = 0; px < stride; ++px) {
             GatherGeom g;
@@ -3707,6 +3718,7 @@ extern "C" int et_conv2d_wgrad_grouped(const et_wgrad_item* items, int n_items, 
     grp.n = n_items;
     for (int i = 0; i < n_items; ++i) {
         if (!items[i].x || !items[i].dy || !items[i].dw) return -1;
+        if (!nhwc_ok(items[i].x, items[i].ldx, Cin, vec) || !nhwc_ok(items[i].dy, items[i].ldy, Cout, vec) || ((uintptr_t)items[i].dw & 15)) return -2;
         grp.it[i].x = (const uint16_t*)items[i].x; grp.it[i].dy = (const uint16_t*)items[i].dy; grp.it[i].dw = items[i].dw;
         grp.it[i].ldx = items[i].ldx; grp.it[i].ldy = items[i].ldy;
     }

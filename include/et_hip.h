@@ -193,6 +193,11 @@ int et_conv2d_stats_adds_for(int op, int dtype, int N, int IH, int IW, int Cin, 
  * itself, so a Conv block is two launches (conv, normalise) instead of three, and one memset per STEP zeroes every layer's shards
  * when they live in one arena.  Sums are then order-dependent in the last fp32 bits (the 16-bit training modes use this form). */
 #define ET_BN_SHARDS 16
+/* Operand layout of the five conv entry points below (et_conv2d_fwd, _dgrad, _dgrad_bn, _wgrad, _wgrad_grouped): every activation
+ * tensor (x, y, dy, dx, residual, bn_y) is NHWC over a pixel stride in elements (ldx, ldy, ldr, ld_bn), so a channel slice of a wider
+ * buffer is an operand.  All kernels move it in 16-byte vectors, hence for each of them: pixel stride >= its channel count, pixel
+ * stride a multiple of 4 (ET_F32) / 8 (16-bit types), base pointer 16-byte aligned; the weight pointers (w, wT, dw) 16-byte aligned
+ * too.  A call that violates one of these returns -2 before anything is launched. */
 int et_conv2d_fwd(const void* x, const void* w, void* y, int dtype, int N, int IH, int IW, int Cin,
                   int ldx, int Cout, int KH, int KW, int stride, int pad, int ldy, const float* scale,
                   const float* bias, int act, const void* residual, int ldr, float* stats_partial, int stats_ld,
