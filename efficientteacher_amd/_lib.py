@@ -28,6 +28,8 @@ SIGNATURES = {
     "et_nms_ssod": (c_int, [P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "et_val_match": (c_int, [P, c_int, P, c_int, c_int, P, c_int, P, c_int, c_int, P, c_int, c_int, c_int, c_int64, c_int64,
                              P, P, P, P, P, P]),
+    "et_val_confusion": (c_int, [P, c_int, P, c_int, c_int, P, c_int, P, c_int, c_int, c_float, c_float, c_int, c_int, P, P]),
+    "et_val_predn": (c_int, [P, c_int, P, c_int, c_int, P, c_int, c_int, c_int, P, P, P]),
     "et_val_ap_workspace_bytes": (c_int, [c_int, ctypes.POINTER(c_size_t)]),
     "et_val_ap": (c_int, [P, P, P, c_int64, P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "et_detect_decode": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64,

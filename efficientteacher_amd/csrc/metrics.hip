@@ -22,6 +22,22 @@
 //                  and every row writes the interpolation points that fall into its own recall (AP, 101 points) or
 //                  confidence (P / R / F1 curves, 1000 points, threshold 0 only) interval.  Integer counts, fp64
 //                  arithmetic in numpy's operation order, no float atomics: results do not depend on scheduling.
+//   et_val_confusion : the reference's ConfusionMatrix.process_batch (utils/metrics.py:137-175) in closed form, one
+//                  workgroup per image, the same label tiles and the same IoU arithmetic as et_val_match (an IoU has the
+//                  same bits in both).  Only images with a label AND an NMS detection count.  Detections with
+//                  conf > conf_thres (strict) take part; the IoU is class-agnostic; a pair qualifies if iou > iou_thres
+//                  (strict).  l*(d) = the qualifying label of largest IoU (equal IoU: the LOWER label index); label l
+//                  is matched to d*(l) = the detection of LARGEST IoU among {d : l*(d) = l} (equal IoU: the LOWER
+//                  detection index) -- the re-sort by IoU that process_batch of val.py leaves out is present here
+//                  (utils/metrics.py:158).  matrix[predicted, true], row / column nc = background:
+//                      every label l            : matrix[nc, cls(l)] += 1
+//                      every winner d = d*(l)   : matrix[nc, cls(l)] -= 1, matrix[cls(d), cls(l)] += 1
+//                      if the image has a match : every other filtered detection d: matrix[cls(d), nc] += 1
+//                  (an image whose detections match nothing adds nothing to column nc: the reference's behaviour).
+//                  int32 atomics only: exact, commutative, two runs are bit-identical.  "d is a winner" is the scan
+//                  over the (l*, IoU) pairs in LDS that val_match_kernel does over (l*, mask).
+//   et_val_predn : elementwise, one thread per (image, NMS slot): scale_coords + clip_coords of the box (val.py:355-356)
+//                  with conf and class copied, and the top-left xywh save_one_json derives from it (val.py:70-71).
 #pragma clang fp contract(off)
 #include "et_device.h"
 #include "../../include/et_hip.h"
@@ -144,6 +160,148 @@ __global__ __launch_bounds__(VM_THREADS) void val_match_kernel(
         cls[row] = v ? (int)dc[q] : -1;
         valid[row] = v ? 1 : 0;
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// class column of a label / detection: truncation towards zero like .int() (utils/metrics.py:148-149); -1 = outside [0, nc)
+__device__ __forceinline__ int vm_class(float c, int nc) { return (c > -1.0f && c < (float)nc) ? (int)c : -1; }
+
+__global__ __launch_bounds__(VM_THREADS) void val_confusion_kernel(
+    const float* __restrict__ dets, int det_stride, const int* __restrict__ counts, int max_det,
+    const float* __restrict__ targets, int NT, const float* __restrict__ shapes, float net_h, float net_w,
+    float conf_thres, float iou_thres, int single_cls, int nc, int* __restrict__ matrix) {
+    __shared__ VmBox l_box[VM_THREADS];
+    __shared__ float l_area[VM_THREADS];
+    __shared__ int l_cls[VM_THREADS];
+    __shared__ int l_ok[VM_THREADS];
+    __shared__ int s_best[VM_MAX_DET];
+    __shared__ float s_iou[VM_MAX_DET];
+    __shared__ int s_any;
+    const int si = blockIdx.x, tid = threadIdx.x;
+    const int n = min(max(counts[si], 0), max_det);
+    if (n == 0) return;                                                // val.py:347-350: not even the labels count
+    const float* sh = shapes + (size_t)si * 5;
+    const float gain = sh[0], padx = sh[1], pady = sh[2], h0 = sh[3], w0 = sh[4];
+    if (tid == 0) s_any = 0;
+
+    VmBox db[VM_PER];
+    float da[VM_PER], best[VM_PER];
+    int dcl[VM_PER], bl[VM_PER], blc[VM_PER];
+    bool keep[VM_PER];
+#pragma unroll
+    for (int q = 0; q < VM_PER; ++q) {
+        const int d = tid + q * VM_THREADS;
+        best[q] = -1.0f; bl[q] = -1; blc[q] = -1; da[q] = 0.f; dcl[q] = -1; keep[q] = false;
+        db[q].x1 = db[q].y1 = db[q].x2 = db[q].y2 = 0.f;
+        if (d < n) {
+            const float* r = dets + ((size_t)si * max_det + d) * det_stride;
+            if (r[4] > conf_thres) {                                   // utils/metrics.py:147, strict
+                keep[q] = true;
+                VmBox b; b.x1 = r[0]; b.y1 = r[1]; b.x2 = r[2]; b.y2 = r[3];
+                db[q] = vm_to_native(b, gain, padx, pady, w0, h0);
+                da[q] = (db[q].x2 - db[q].x1) * (db[q].y2 - db[q].y1);
+                dcl[q] = single_cls ? 0 : vm_class(r[5], nc);          // val.py:353-354
+            }
+        }
+    }
+
+    const int bg = nc * (nc + 1);                                      // row nc: background
+    for (int base = 0; base < NT; base += VM_THREADS) {
+        __syncthreads();
+        const int t = base + tid;
+        int ok = 0;
+        if (t < NT) {
+            const float* g = targets + (size_t)t * 6;
+            if (g[0] == (float)si) {                                   // val.py:341
+                ok = 1;
+                VmBox b;
+                if (net_w == 0.0f) {                                   // corner rows [img, cls, x1, y1, x2, y2]: process_batch's labels
+                    b.x1 = g[2]; b.y1 = g[3]; b.x2 = g[4]; b.y2 = g[5];
+                } else {
+                    const float x = g[2] * net_w, y = g[3] * net_h, w = g[4] * net_w, h = g[5] * net_h;   // val.py:328
+                    b.x1 = x - w / 2; b.y1 = y - h / 2; b.x2 = x + w / 2; b.y2 = y + h / 2;   // xywh2xyxy, utils/general.py:630
+                }
+                b = vm_to_native(b, gain, padx, pady, w0, h0);
+                const int c = vm_class(g[1], nc);
+                l_box[tid] = b;
+                l_area[tid] = (b.x2 - b.x1) * (b.y2 - b.y1);
+                l_cls[tid] = c;
+                if (c >= 0) atomicAdd(&matrix[bg + c], 1);             // unmatched until a winner takes it back
+            }
+        }
+        l_ok[tid] = ok;
+        __syncthreads();
+        const int lim = min(VM_THREADS, NT - base);
+        for (int k = 0; k < lim; ++k) {
+            if (!l_ok[k]) continue;                                    // block-uniform
+            const VmBox lb = l_box[k];
+            const float la = l_area[k];
+            const int lc = l_cls[k];
+#pragma unroll
+            for (int q = 0; q < VM_PER; ++q) {
+                if (keep[q]) {                                         // class-agnostic, utils/metrics.py:150
+                    const float iw = fmaxf(fminf(lb.x2, db[q].x2) - fmaxf(lb.x1, db[q].x1), 0.0f);
+                    const float ih = fmaxf(fminf(lb.y2, db[q].y2) - fmaxf(lb.y1, db[q].y1), 0.0f);
+                    const float inter = iw * ih;
+                    const float iou = inter / (la + da[q] - inter);    // utils/metrics.py:274
+                    // :152 strict; strict again: the lower label index keeps a tie
+                    if (iou > iou_thres && iou > best[q]) { best[q] = iou; bl[q] = base + k; blc[q] = lc; }
+                }
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < VM_PER; ++q) {
+        const int d = tid + q * VM_THREADS;
+        if (d < n) { s_best[d] = bl[q]; s_iou[d] = best[q]; }
+        if (bl[q] >= 0) s_any = 1;                                     // every chosen label has a winner: the image has a match
+    }
+    __syncthreads();
+    const int any = s_any;
+#pragma unroll
+    for (int q = 0; q < VM_PER; ++q) {
+        const int d = tid + q * VM_THREADS;
+        if (!keep[q]) continue;
+        bool win = bl[q] >= 0;
+        if (win)
+            for (int e = 0; e < n; ++e)                                // :158-159: the label keeps its detection of largest IoU
+                if (s_best[e] == bl[q] && (s_iou[e] > best[q] || (s_iou[e] == best[q] && e < d))) { win = false; break; }
+        if (win) {
+            if (blc[q] >= 0) {
+                atomicAdd(&matrix[bg + blc[q]], -1);
+                if (dcl[q] >= 0) atomicAdd(&matrix[dcl[q] * (nc + 1) + blc[q]], 1);   // :168
+            }
+        } else if (any && dcl[q] >= 0) {
+            atomicAdd(&matrix[dcl[q] * (nc + 1) + nc], 1);             // :172-175
+        }
+    }
+}
+
+__global__ __launch_bounds__(VM_THREADS) void val_predn_kernel(const float* __restrict__ dets, int det_stride,
+                                                               const int* __restrict__ counts, long long rows, int max_det,
+                                                               const float* __restrict__ shapes, int single_cls,
+                                                               float* __restrict__ predn, float* __restrict__ xywh_tl) {
+    const long long row = (long long)blockIdx.x * VM_THREADS + threadIdx.x;
+    if (row >= rows) return;
+    const int si = (int)(row / max_det), d = (int)(row - (long long)si * max_det);
+    float o[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, t[4] = {0.f, 0.f, 0.f, 0.f};
+    if (d < min(max(counts[si], 0), max_det)) {
+        const float* sh = shapes + (size_t)si * 5;
+        const float* r = dets + (size_t)row * det_stride;
+        VmBox b; b.x1 = r[0]; b.y1 = r[1]; b.x2 = r[2]; b.y2 = r[3];
+        b = vm_to_native(b, sh[0], sh[1], sh[2], sh[4], sh[3]);
+        o[0] = b.x1; o[1] = b.y1; o[2] = b.x2; o[3] = b.y2; o[4] = r[4];
+        o[5] = single_cls ? 0.0f : r[5];                               // val.py:353-354
+        const float w = b.x2 - b.x1, h = b.y2 - b.y1;                  // xyxy2xywh, utils/general.py:549-556
+        t[0] = (b.x1 + b.x2) / 2 - w / 2;                              // val.py:71: centre to top-left corner
+        t[1] = (b.y1 + b.y2) / 2 - h / 2;
+        t[2] = w; t[3] = h;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) predn[row * 6 + k] = o[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xywh_tl[row * 4 + k] = t[k];
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -322,6 +480,34 @@ extern "C" int et_val_match(const float* dets, int det_row_stride, const int* co
     hipLaunchKernelGGL(val_match_kernel, dim3(B), dim3(VM_THREADS), 0, (hipStream_t)stream, dets, det_row_stride, counts,
                        max_det, targets, NT, shapes, (float)net_h, (float)net_w, iouv, niou, single_cls ? 1 : 0, nc,
                        (long long)row_offset, correct, conf, cls, valid, nt);
+    ET_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int et_val_confusion(const float* dets, int det_row_stride, const int* counts, int B, int max_det,
+                                const float* targets, int NT, const float* shapes, int net_h, int net_w, float conf_thres,
+                                float iou_thres, int single_cls, int nc, int* matrix, et_stream_t stream) {
+    if (B < 0 || NT < 0 || max_det <= 0 || max_det > VM_MAX_DET) return -2;
+    if (B == 0) return 0;
+    if (det_row_stride < 6 || nc <= 0 || nc > 32767 || net_h < 0 || net_w < 0 || (net_h == 0) != (net_w == 0)) return -2;
+    if (!dets || !counts || !shapes || !matrix || (NT > 0 && !targets)) return -1;
+    hipLaunchKernelGGL(val_confusion_kernel, dim3(B), dim3(VM_THREADS), 0, (hipStream_t)stream, dets, det_row_stride, counts,
+                       max_det, targets, NT, shapes, (float)net_h, (float)net_w, conf_thres, iou_thres, single_cls ? 1 : 0, nc,
+                       matrix);
+    ET_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int et_val_predn(const float* dets, int det_row_stride, const int* counts, int B, int max_det, const float* shapes,
+                            int net_h, int net_w, int single_cls, float* predn, float* xywh_tl, et_stream_t stream) {
+    if (B < 0 || max_det <= 0 || max_det > VM_MAX_DET) return -2;
+    if (B == 0) return 0;
+    if (det_row_stride < 6 || net_h <= 0 || net_w <= 0) return -2;
+    if (!dets || !counts || !shapes || !predn || !xywh_tl) return -1;
+    const long long rows = (long long)B * max_det;
+    hipLaunchKernelGGL(val_predn_kernel, dim3((unsigned)((rows + VM_THREADS - 1) / VM_THREADS)), dim3(VM_THREADS), 0,
+                       (hipStream_t)stream, dets, det_row_stride, counts, rows, max_det, shapes, single_cls ? 1 : 0, predn,
+                       xywh_tl);
     ET_CHECK_LAUNCH();
     return 0;
 }

@@ -878,6 +878,43 @@ def val_match(dets, counts, targets, shapes, net_hw, iouv, nc, correct, conf, cl
                                         _lib.stream(conf)), "et_val_match")
 
 
+def _val_batch_operands(dets, counts, shapes):
+    B, max_det = dets.shape[0], dets.shape[1]
+    if dets.dtype != torch.float32 or dets.stride(2) != 1 or (B > 1 and dets.stride(0) != max_det * dets.stride(1)):
+        dets = dets.float().contiguous()
+    assert counts.dtype == torch.int32 and counts.numel() == B and counts.is_contiguous()
+    assert shapes.dtype == torch.float32 and shapes.shape == (B, 5) and shapes.is_contiguous()
+    return dets, B, max_det
+
+
+def val_confusion(dets, counts, targets, shapes, net_hw, nc, matrix, conf_thres=0.25, iou_thres=0.45, single_cls=False):
+    """one validation batch of ConfusionMatrix.process_batch (utils/metrics.py:137-175, csrc/metrics.hip): the operands of
+    ``val_match``; matrix (nc+1, nc+1) int32 [predicted, true] is accumulated into.  Stream-ordered, no host synchronisation."""
+    dets, B, max_det = _val_batch_operands(dets, counts, shapes)
+    targets = targets.reshape(-1, 6)
+    if targets.dtype != torch.float32 or not targets.is_contiguous():
+        targets = targets.float().contiguous()
+    assert matrix.dtype == torch.int32 and matrix.shape == (nc + 1, nc + 1) and matrix.is_contiguous()
+    NT = targets.shape[0]
+    _lib.check(_lib.load().et_val_confusion(_lib.ptr(dets), dets.stride(1), _lib.ptr(counts), B, max_det,
+                                            _lib.ptr(targets) if NT else None, NT, _lib.ptr(shapes), int(net_hw[0]),
+                                            int(net_hw[1]), float(conf_thres), float(iou_thres), int(bool(single_cls)), int(nc),
+                                            _lib.ptr(matrix), _lib.stream(matrix)), "et_val_confusion")
+
+
+def val_predn(dets, counts, shapes, net_hw, single_cls=False):
+    """the native-space predictions of one validation batch (val.py:355-356) and the top-left xywh boxes save_one_json derives
+    from them (val.py:70-71): -> predn (B, max_det, 6), xywh_tl (B, max_det, 4) fp32 on the device, padding rows zero.
+    Stream-ordered, no host synchronisation."""
+    dets, B, max_det = _val_batch_operands(dets, counts, shapes)
+    predn = torch.empty((B, max_det, 6), dtype=torch.float32, device=dets.device)
+    xywh_tl = torch.empty((B, max_det, 4), dtype=torch.float32, device=dets.device)
+    _lib.check(_lib.load().et_val_predn(_lib.ptr(dets), dets.stride(1), _lib.ptr(counts), B, max_det, _lib.ptr(shapes),
+                                        int(net_hw[0]), int(net_hw[1]), int(bool(single_cls)), _lib.ptr(predn),
+                                        _lib.ptr(xywh_tl), _lib.stream(predn)), "et_val_predn")
+    return predn, xywh_tl
+
+
 def val_ap(cls_sorted, correct_sorted, conf_sorted, nt, niou):
     """ap_per_class + compute_ap (utils/metrics.py:22-126) over rows ordered by (class, conf descending), padding rows (class >= nc)
     last -> ap (nc, niou), p, r, f1 (nc, 1000) fp64 on the device; rows of classes without labels or predictions are zero"""

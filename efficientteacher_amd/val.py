@@ -16,13 +16,18 @@ positions, no device->host transfer and no synchronisation -- and ``compute`` is
 copy of a few KB to the host: P, R, AP per class and threshold, F1, the per-class F1-optimal confidence thresholds
 (``cls_thr``, which SSOD validation hands back to the trainer) and ``fitness``.
 
-``run`` is the reference's ``val.run`` over the two for a model and a loader that already exist (its ``training`` branch).
-Its ConfusionMatrix, plots, save_txt / save_json / pycocotools legs and the keypoint (num_points) variants are host code of the
-reference and stay there.
+``ConfusionMatrix`` (utils/metrics.py:129-204) is the same on the device: ``update`` is one et_val_confusion launch per batch into
+an int32 (nc+1, nc+1) matrix, reading ``matrix`` is the one transfer.  ``native_predictions`` / ``coco_json_rows`` are the ``predn``
+of val.py:355-356 and the rows ``save_one_json`` (val.py:67-76) appends, from one et_val_predn launch and one transfer per batch.
+
+``run`` is the reference's ``val.run`` over these for a model and a loader that already exist (its ``training`` branch).  Its
+``confusion_matrix=`` / ``jdict=`` keywords collect the two above; the plots, save_txt / save_json / pycocotools legs behind the
+reference's own flags and the keypoint (num_points) variants are host code of the reference and stay there.
 """
 import torch
 
 import time
+from pathlib import Path
 
 import numpy as np
 
@@ -105,14 +110,139 @@ def shape_rows(shapes, net_hw):
     return torch.tensor(rows, dtype=torch.float32).reshape(-1, 5)
 
 
+def _device_shapes(shapes, net_hw, device):
+    """``shapes`` of one batch as the (B, 5) fp32 device rows the kernels take: a tensor as it is, the loader's list through
+    ``shape_rows`` and one stream-ordered copy"""
+    if not torch.is_tensor(shapes):
+        shapes = shape_rows(shapes, net_hw)
+        if device.type == "cuda":
+            shapes = shapes.pin_memory()
+    return shapes.to(device, torch.float32, non_blocking=True).contiguous()
+
+
+class ConfusionMatrix:
+    """The reference's ConfusionMatrix (utils/metrics.py:129-204), device resident: ``matrix[predicted, true]`` with row / column nc
+    as background, accumulated by et_val_confusion (the closed form: include/et_hip.h) in int32.
+
+    Where the reference leaves the outcome to an unstable argsort: of two qualifying labels of exactly equal IoU a detection takes
+    the lower label index; of two detections of exactly equal IoU a label takes the lower detection index."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45, device=None):
+        self.nc, self.conf, self.iou_thres = int(nc), float(conf), float(iou_thres)
+        self.device = torch.device(device if device is not None else "cuda")
+        self.reset()
+
+    def reset(self):
+        self._m = torch.zeros((self.nc + 1, self.nc + 1), dtype=torch.int32, device=self.device)
+
+    def update(self, dets, counts, targets, shapes, net_hw, single_cls=False):
+        """one batch, the arguments of ``DetectionMetrics.update``: one launch, no transfer, no synchronisation"""
+        assert 1 <= dets.shape[1] <= 1024, dets.shape
+        shapes = _device_shapes(shapes, net_hw, self.device)
+        ops.val_confusion(dets, counts, targets, shapes, net_hw, self.nc, self._m, self.conf, self.iou_thres, single_cls)
+
+    def process_batch(self, detections, labels):
+        """the reference's signature: one image, detections (N, 6) [x1,y1,x2,y2,conf,cls] and labels (M, 5) [cls,x1,y1,x2,y2] in
+        native space, coordinates >= 0 as scale_coords leaves them.  The same kernel over corner-form label rows and an identity shape
+        row (gain 1, pad 0, no upper clip), so the counts equal ``update``'s on the same image."""
+        dev = self.device
+        det = torch.as_tensor(detections, dtype=torch.float32).to(dev).reshape(-1, 6)
+        lab = torch.as_tensor(labels, dtype=torch.float32).to(dev).reshape(-1, 5)
+        if det.shape[0] == 0:                                        # no row passes the conf filter; the labels still count (:165-170)
+            det = torch.tensor([[0.0, 0.0, 0.0, 0.0, float("-inf"), 0.0]], device=dev)
+        n = det.shape[0]
+        if n > 1024:
+            raise ValueError(f"process_batch takes at most 1024 detections of one image, got {n}")
+        targets = torch.cat((torch.zeros_like(lab[:, :1]), lab), 1)
+        row = torch.tensor([[1.0, 0.0, 0.0, float("inf"), float("inf")]], device=dev)
+        counts = torch.full((1,), n, dtype=torch.int32, device=dev)
+        ops.val_confusion(det.reshape(1, n, 6).contiguous(), counts, targets, row, (0, 0), self.nc, self._m, self.conf,
+                          self.iou_thres, False)
+
+    def matrix_device(self):
+        """the (nc+1, nc+1) int32 device tensor the kernel accumulates into"""
+        return self._m
+
+    @property
+    def matrix(self):
+        """(nc+1, nc+1) float64 numpy array, as the reference holds it: the one transfer"""
+        return self._m.cpu().numpy().astype(np.float64)
+
+    def print(self):
+        for row in self.matrix:
+            print(' '.join(map(str, row)))
+
+    def plot(self, normalize=True, save_dir='', names=()):
+        """confusion_matrix.png in save_dir: columns normalised to sum 1 (normalize), cells below 0.005 left blank, class names on the
+        ticks when there are nc of them (fewer than 99).  Host code; a missing seaborn / matplotlib is a warning, not an error."""
+        try:
+            import warnings
+            import matplotlib.pyplot as plt
+            import seaborn as sn
+            m = self.matrix
+            if normalize:
+                m = m / (m.sum(0, keepdims=True) + 1E-6)
+            m[m < 0.005] = np.nan
+            names = list(names)
+            named = 0 < len(names) < 99 and len(names) == self.nc
+            fig = plt.figure(figsize=(12, 9), tight_layout=True)
+            sn.set(font_scale=0.8 if self.nc >= 50 else 1.0)
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')                      # an all-NaN matrix
+                ax = sn.heatmap(m, annot=self.nc < 30, annot_kws={"size": 8}, cmap='Blues', fmt='.2f', square=True,
+                                xticklabels=names + ['background FP'] if named else "auto",
+                                yticklabels=names + ['background FN'] if named else "auto")
+            ax.set_facecolor((1, 1, 1))
+            ax.set_xlabel('True')
+            ax.set_ylabel('Predicted')
+            fig.savefig(Path(save_dir) / 'confusion_matrix.png', dpi=250)
+            plt.close(fig)
+        except Exception as e:
+            print(f'WARNING: ConfusionMatrix plot failure: {e}')
+
+
+def native_predictions(dets, counts, shapes, net_hw, single_cls=False):
+    """``predn`` of val.py:355-356 for a padded batch (``infer_batch(padded=True)``): -> predn (B, max_det, 6) [x1,y1,x2,y2 in the
+    native image, conf, cls] and xywh_tl (B, max_det, 4), the top-left xywh box save_one_json writes -- device tensors, padding rows
+    zero, one launch, no transfer.  shapes as ``DetectionMetrics.update`` takes them."""
+    return ops.val_predn(dets, counts, _device_shapes(shapes, net_hw, dets.device), net_hw, single_cls=single_cls)
+
+
+def image_id_of_path(path):
+    """save_one_json's image id (val.py:69): the file stem, as an int when it is numeric"""
+    stem = Path(path).stem
+    return int(stem) if stem.isnumeric() else stem
+
+
+def coco_json_rows(predn, xywh_tl, counts, image_ids, class_map=None):
+    """the dicts save_one_json (val.py:67-76) appends for a batch, from ``native_predictions``' tensors: one transfer (a single
+    list conversion), then the reference's round(x, 3) / round(score, 5) on the host.  class_map: category id by class index (the
+    reference's coco80_to_91_class() list); None = the class index itself."""
+    B, max_det = predn.shape[0], predn.shape[1]
+    assert len(image_ids) == B and xywh_tl.shape[:2] == (B, max_det)
+    if B == 0:
+        return []
+    n = counts.to(torch.float32).reshape(B, 1, 1).expand(B, max_det, 1)
+    host = torch.cat((predn, xywh_tl, n), 2).tolist()
+    rows = []
+    for image_id, img in zip(image_ids, host):
+        for r in img[:min(max(int(img[0][10]), 0), max_det)]:
+            c = int(r[5])
+            rows.append({'image_id': image_id, 'category_id': c if class_map is None else class_map[c],
+                         'bbox': [round(x, 3) for x in r[6:10]], 'score': round(r[4], 5)})
+    return rows
+
+
 class DetectionMetrics:
-    """Device-resident P / R / mAP accumulator (see the module docstring).
+    """Device-resident P / R / mAP accumulator (see the module docstring).  ``confusion``: a ``ConfusionMatrix`` that ``update`` feeds
+    with the same batch (one more launch); None: nothing else runs.
 
     Order rules the reference leaves to unstable sorts: a detection with two class-matching labels of exactly equal IoU takes the
     lower label index; detections of equal confidence are ranked in arena order (image, then NMS rank)."""
 
-    def __init__(self, nc, iouv=None, max_det=300, device=None):
+    def __init__(self, nc, iouv=None, max_det=300, device=None, confusion=None):
         self.nc, self.max_det = int(nc), int(max_det)
+        self.confusion = confusion
         self.device = torch.device(device if device is not None else "cuda")
         iouv = torch.linspace(0.5, 0.95, 10) if iouv is None else torch.as_tensor(iouv)          # val.py:244
         self.iouv = iouv.detach().to("cpu", torch.float32).contiguous().to(self.device)
@@ -154,6 +284,8 @@ class DetectionMetrics:
                       row_offset=self._rows, single_cls=single_cls)
         self._rows += B * self.max_det
         self.seen += B
+        if self.confusion is not None:
+            self.confusion.update(dets, counts, targets, shapes, net_hw, single_cls=single_cls)
 
     def rows(self):
         """the arena so far: correct (bit i = true positive at iouv[i]), conf, cls, valid -- device tensors, one row per
@@ -212,12 +344,15 @@ class DetectionMetrics:
 @torch.no_grad()
 def run(model, dataloader, *, conf_thres=0.001, iou_thres=0.6, half=True, single_cls=False, augment=False, compute_loss=None,
         val_ssod=False, nc=80, names=None, eval_num=-1, verbose=False, max_det=300, save_txt=False, save_json=False,
-        save_hybrid=False, plots=False, num_points=0):
+        save_hybrid=False, plots=False, num_points=0, confusion_matrix=None, jdict=None, image_id_of=None, class_map=None):
     """The reference's val.run (val.py:149-465) for a model and a loader that exist (its ``training`` branch):
     returns ((mp, mr, map50, map, *loss), maps, t) and, with val_ssod, cls_thr as a fourth element; prints its table.
     The three loss entries are zeros as in the reference, whose compute_loss call is unreachable (val.py:307 is always true);
     ``compute_loss`` is accepted for call compatibility.  t = (pre-process, inference + NMS + matching, 0) ms per image: the stages
-    are not separated by device synchronisations here."""
+    are not separated by device synchronisations here.
+    confusion_matrix: a ``ConfusionMatrix`` to accumulate over the loop (val.py:372-373).  jdict: a list that receives the rows
+    save_one_json would append (val.py:381-382), ``image_id_of(path)`` (default: the reference's stem rule) and ``class_map`` as in
+    ``coco_json_rows``.  Both default to off and change nothing else; plots / save_json / save_txt themselves keep raising."""
     for flag, what in ((save_txt, "save_txt (val.py:379)"), (save_json, "save_json / pycocotools (val.py:381, :428-452)"),
                        (save_hybrid, "save_hybrid autolabelling (val.py:330)"), (plots, "plots / ConfusionMatrix (val.py:372, :386, :423)"),
                        (num_points, "num_points keypoint validation (val.py:332, :357-364)")):
@@ -230,7 +365,11 @@ def run(model, dataloader, *, conf_thres=0.001, iou_thres=0.6, half=True, single
         names = getattr(inner, "names", None) or {}
     if isinstance(names, (list, tuple)):
         names = dict(enumerate(names))
-    metrics = DetectionMetrics(nc, max_det=max_det, device=device)
+    if confusion_matrix is not None:
+        assert confusion_matrix.nc == nc, (confusion_matrix.nc, nc)
+    metrics = DetectionMetrics(nc, max_det=max_det, device=device, confusion=confusion_matrix)
+    if jdict is not None and image_id_of is None:
+        image_id_of = image_id_of_path
     s = ('%20s' + '%11s' * 6) % ('Class', 'Images', 'Labels', 'P', 'R', 'mAP@.5', 'mAP@.5:.95')
     dt = [0.0, 0.0, 0.0]
     nbatches = 0
@@ -243,7 +382,12 @@ def run(model, dataloader, *, conf_thres=0.001, iou_thres=0.6, half=True, single
         t2 = time.perf_counter()
         (dets, counts), _ = infer_batch(model, img, conf_thres, iou_thres, half=half, augment=augment, single_cls=single_cls,
                                         max_det=max_det, padded=True)
+        if jdict is not None:
+            shapes = _device_shapes(shapes, img.shape[2:], device)
+            predn, xywh_tl = native_predictions(dets, counts, shapes, img.shape[2:], single_cls=single_cls)
         metrics.update(dets, counts, targets, shapes, img.shape[2:], single_cls=single_cls)
+        if jdict is not None:                                        # after the launches: the transfer waits for all of them at once
+            jdict.extend(coco_json_rows(predn, xywh_tl, counts, [image_id_of(p) for p in paths], class_map))
         dt[0] += t2 - t1
         dt[1] += time.perf_counter() - t2
         nbatches += 1

@@ -31,7 +31,7 @@ enum { ET_F32 = 0, ET_BF16 = 1, ET_F16 = 2 };   /* ET_F16 (r05): IEEE half stora
  * for ("gfx950") and the ABI version.  ET_ABI_VERSION changes whenever an entry point is added or a signature / workspace
  * contract changes; a binding must refuse a library whose et_abi_version() differs from the header it was written against
  * (efficientteacher_amd/_lib.py does): a stale libet_hip.so would otherwise read e.g. a new int argument as the stream. */
-#define ET_ABI_VERSION 8
+#define ET_ABI_VERSION 9
 const char* et_build_arch(void);
 int et_abi_version(void);
 
@@ -84,6 +84,45 @@ int et_nms(const float* pred, int B, int A, int no, float conf_thres, float iou_
 int et_val_match(const float* dets, int det_row_stride, const int* counts, int B, int max_det, const float* targets, int NT,
                  const float* shapes, int net_h, int net_w, const float* iouv, int niou, int single_cls, int nc,
                  int64_t row_offset, int64_t arena_rows, int* correct, float* conf, int* cls, int* valid, int* nt,
+                 et_stream_t stream);
+
+/* et_val_confusion replaces ConfusionMatrix.process_batch (utils/metrics.py:137-175) as val.py:340-373 reaches it, for one
+ * batch, in closed form.  Inputs are exactly those of et_val_match (dets / counts / targets / shapes as above).
+ *   matrix  ((nc+1), (nc+1)) int32, matrix[predicted * (nc+1) + true], row / column nc = background; ACCUMULATED into, not
+ *           cleared (integer atomics only: exact, and two runs are bit-identical)
+ * Per image, only if it has at least one label AND at least one NMS detection (an image without detections contributes
+ * nothing, not even its labels: val.py:347-350 continues first):
+ *   1. the detections with conf > conf_thres (strict) take part; the reference's default is 0.25;
+ *   2. IoU of every (label, detection) pair in native space, CLASS-AGNOSTIC; a pair qualifies if iou > iou_thres (strict;
+ *      default 0.45);
+ *   3. detection d keeps l*(d), its qualifying label of largest IoU (first np.unique, :157);
+ *   4. label l keeps d*(l), the detection of LARGEST IoU among {d : l*(d) = l} -- the re-sort by IoU that val.py's
+ *      process_batch has commented out is present here (:158-159); the matches {(l, d*(l))} are one-to-one;
+ *   5. every matched label: matrix[cls(d*(l)), cls(l)] += 1; every unmatched label: matrix[nc, cls(l)] += 1; and ONLY IF
+ *      the image has at least one match, every filtered detection that is no d*(l): matrix[cls(d), nc] += 1.  An image
+ *      whose detections match nothing adds nothing to column nc (the reference's `if n:` at :172).
+ *   6. classes are truncated to int (.int()); single_cls: every detection is class 0 (val.py:353-354).  A count whose
+ *      label or detection class falls outside [0, nc) is not made (the reference would index out of range).
+ * Tie rules where the reference leaves the outcome to an unstable argsort()[::-1]: two qualifying labels of exactly equal
+ * IoU for one detection -> the LOWER label index (target row order); two detections of exactly equal IoU for one label ->
+ * the LOWER detection index (NMS order).
+ * The IoU arithmetic is et_val_match's (fp32, the reference's operation order, true division by gain).
+ * net_h == net_w == 0: the target rows are [img, cls, x1, y1, x2, y2], corners in the detections' own space (the labels
+ * as process_batch takes them); they go through `shapes` like the detections (an identity row [1, 0, 0, inf, inf] leaves
+ * non-negative coordinates as they are), nothing else changes.
+ * Limits: max_det <= 1024, nc <= 32767; no limit on labels per image; no workspace.  B == 0 is a no-op. */
+int et_val_confusion(const float* dets, int det_row_stride, const int* counts, int B, int max_det, const float* targets,
+                     int NT, const float* shapes, int net_h, int net_w, float conf_thres, float iou_thres, int single_cls,
+                     int nc, int* matrix /*(nc+1)^2*/, et_stream_t stream);
+
+/* et_val_predn: the native-space predictions of val.py:355-356 for one batch, elementwise, one launch.
+ *   predn   (B, max_det, 6) fp32 rows [x1,y1,x2,y2,conf,cls]: scale_coords + clip_coords (utils/general.py:702-773) of each
+ *           detection's box, conf copied, cls copied (0 under single_cls)
+ *   xywh_tl (B, max_det, 4) fp32 rows [x, y, w, h] with xy the TOP-LEFT corner, as save_one_json derives it (val.py:70-71:
+ *           xyxy2xywh, then xy -= wh / 2, in that operation order -- not simply x1, y1)
+ * Rows at or past counts[si] are zero in both. */
+int et_val_predn(const float* dets, int det_row_stride, const int* counts, int B, int max_det, const float* shapes,
+                 int net_h, int net_w, int single_cls, float* predn /*(B, max_det, 6)*/, float* xywh_tl /*(B, max_det, 4)*/,
                  et_stream_t stream);
 
 /* et_val_ap replaces utils/metrics.py:22-126 (ap_per_class + compute_ap, without the plots) once per evaluation.
