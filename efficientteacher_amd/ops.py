@@ -87,7 +87,7 @@ class FamilyTimer:
 def kernel_name(op, dtype, N, IH, IW, Cin, Cout, k, stride, pad, parity_class=0, zero_page=True):
     """Name of the kernel instantiation the library launches for this conv problem (op: 'fwd' | 'dgrad' | 'wgrad', and
     'dgrad_full' / 'fwd_res' = the same with a residual / accumulate / BN-backward sums in the epilogue -- the persistent 1x1 kernel
-    has separate instantiations for those; arguments of the FORWARD conv), as rocprofv3 prints it.  The selection lives in csrc/conv.hip only
+    has separate instantiations for those; arguments of the FORWARD conv), as rocprofv3 prints it.  The selection lives in csrc/conv_host.hip only
     (et_conv2d_kernel_name); tests assert on it and bench.py tags its HIP-event timings with it."""
     import ctypes
     buf = ctypes.create_string_buffer(256)

@@ -197,11 +197,11 @@ def test_conv_wgrad_grouped(hip, dtype):
 
 # ---- every kernel instantiation the YOLOv5l / YOLOv5s bench launches, selected on purpose ----------------------
 # (VERDICT r01 "parity gap": the bench-dominant tiles were never compared element-wise with anything.)  Each case
-# names the instantiation csrc/conv.hip must pick for it -- et_conv2d_kernel_name is the selection logic itself, not
+# names the instantiation csrc/conv_host.hip must pick for it -- et_conv2d_kernel_name is the selection logic itself, not
 # a copy -- so a change of the tile policy that silently drops a kernel out of test coverage fails here.
 GLDS = "conv_gemm_glds_kernel<"
 RS128, RS64 = "conv_gemm_rs_kernel<128, 128, 2, 2>", "conv_gemm_rs_kernel<128, 64, 2, 2>"
-S1 = "conv1x1_stream_kernel<"          # prefix: the shape table behind it (csrc/conv.hip ET_S1_ROWS) is pinned by test_stream_kernel_shape_table below
+S1 = "conv1x1_stream_kernel<"          # prefix: the shape table behind it (csrc/conv_host.h ET_S1_ROWS) is pinned by test_stream_kernel_shape_table below
 SELECT = [
     # N, H, W, Cin, Cout, k, s, p, fwd kernel, dgrad kernels (per parity class), wgrad kernel
     ((2, 20, 20, 256, 256, 3, 1, 1), "conv_gemm_pprs_kernel", ["conv_gemm_pprs_kernel"], "conv_wgrad_rs_kernel<128, 128, 2, 4>"),
@@ -307,7 +307,7 @@ def test_kernel_names_carry_the_storage_type(hip):
     assert ops.kernel_name("fwd", torch.float32, 2, 12, 12, 64, 64, 1, 1, 0).startswith("conv_gemm_glds_kernel<float, ")
 
 
-# conv1x1_stream_kernel's instantiations (csrc/conv.hip ET_S1_ROWS): (full epilogue, Cin, Cout) -> KC, WN, TN, WM, TMW, NS, WGS
+# conv1x1_stream_kernel's instantiations (csrc/conv_host.h ET_S1_ROWS): (full epilogue, Cin, Cout) -> KC, WN, TN, WM, TMW, NS, WGS
 STREAM_SHAPES = {
     (False, 256, 256): (4, 4, 2, 1, 1, 8, 2), (False, 256, 128): (4, 2, 2, 2, 1, 6, 2),
     (False, 128, 256): (2, 4, 2, 1, 2, 6, 2), (False, 128, 128): (2, 2, 2, 2, 2, 3, 2), (False, 128, 64): (2, 1, 2, 4, 1, 3, 2),

@@ -198,8 +198,8 @@ def _need_memory(dev, device_gb, host_gb):
                          ids=["1x1-41x320x320x256", "3x3-82x320x320x128"])
 def test_operands_beyond_2_31_bytes_bit_equal(dev, N, H, W, C, k, family):
     """C -> C stride-1 layers whose bf16 activation (x for forward and wgrad, dy for dgrad and wgrad) spans [2**31 bytes, 2**31
-    elements): the library stages such an operand through flat 64-bit addresses instead of buffer descriptors (csrc/conv.hip: `<
-    (1ull << 31)` bytes in launch_gemm for the stream and row-shift kernels and in the 1x1 weight gradient) and rejects 2**31 elements.
+    elements): the library stages such an operand through flat 64-bit addresses instead of buffer descriptors (`< (1ull << 31)` bytes
+    in csrc/conv.hip's launch_gemm_row for the stream and row-shift kernels and in csrc/conv_host.hip's launch_wgrad for the 1x1 weight gradient) and rejects 2**31 elements.
     et_conv2d_kernel_name reports the kernel FAMILY only -- the flat twin carries the same plan and the name does not tell the two
     forms apart -- so the selection is pinned by the size predicate itself, evaluated here on the operand, with ET_CONV_BUF_DMA unset.
     Forward, dgrad and wgrad are compared in EVERY element; the reference is built a few images at a time (the images of a batch are

@@ -2,7 +2,7 @@
 result of et_conv2d_kernel_name (ops 0..4, every parity class), et_conv2d_stem_kernel_name, et_conv2d_stats_rows_for and
 et_conv2d_stats_adds_for (ops 0..2).  Host only (no GPU needed: device_cus() falls back to 256 compute units, the MI355X's count).
 
-A change of csrc/conv.hip's host layer that is meant to leave the kernel selection alone is checked by dumping before and after and
+A change of the conv host layer (csrc/conv_host.hip; csrc/conv_host.h holds the row lists it selects from) that is meant to leave the kernel selection alone is checked by dumping before and after and
 diffing the two files:
     python tools/conv_plan_dump.py --lib <old libet_hip.so> > old.txt;  python tools/conv_plan_dump.py > new.txt;  diff old.txt new.txt
 
