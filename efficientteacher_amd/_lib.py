@@ -82,6 +82,8 @@ SIGNATURES = {
     "et_mosaic4_u8": (c_int, [P, P, c_int, c_int, c_int, P]),
     "et_pseudo_label_transform": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "et_score_log_append": (c_int, [P, P, c_int, c_int, P, P, P, c_int64, P]),
+    "et_pseudo_quality_workspace_bytes": (c_int, [c_int, ctypes.POINTER(c_size_t)]),
+    "et_pseudo_quality": (c_int, [P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, P, P]),
     "et_yolo_loss": (c_int, [P, P]),
     "et_ota_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "et_ota_assign": (c_int, [P, P, c_float, c_int, P, P, P]),
@@ -127,7 +129,8 @@ _emulated = False
 CALL_TIMER = None
 _NO_LAUNCH = frozenset(n for n in (
     "et_build_arch", "et_abi_version", "et_nms_ssod_workspace_bytes", "et_nms_workspace_bytes", "et_conv2d_stats_rows", "et_conv2d_stats_rows_for",
-    "et_conv2d_kernel_name", "et_conv2d_stem_kernel_name", "et_env_knobs", "et_bn_reduce_rows", "et_ota_workspace_bytes", "et_tal_assign_workspace_bytes", "et_val_ap_workspace_bytes"))
+    "et_conv2d_kernel_name", "et_conv2d_stem_kernel_name", "et_env_knobs", "et_bn_reduce_rows", "et_ota_workspace_bytes", "et_tal_assign_workspace_bytes", "et_val_ap_workspace_bytes",
+    "et_pseudo_quality_workspace_bytes"))
 
 
 class _TimedDll:

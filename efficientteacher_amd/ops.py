@@ -51,7 +51,7 @@ class FamilyTimer:
         "et_conv2d_wgrad": "wgrad", "et_conv2d_wgrad_grouped": "wgrad", "et_conv2d_stem_u8_fwd": "gather_gemm", "et_conv2d_stem_u8_wgrad": "wgrad",
         "et_bn_finalize": "bn", "et_bn_act_fwd": "bn", "et_bn_act_fwd_sharded": "bn", "et_bn_act_bwd_sharded": "bn", "et_bn_act_bwd": "bn", "et_bn_act_bwd_from_partials": "bn", "et_act_bwd": "bn",
         "et_nms": "nms_loss_pl", "et_nms_ssod": "nms_loss_pl", "et_detect_decode": "nms_loss_pl", "et_pseudo_label_transform": "nms_loss_pl",
-        "et_select_targets": "nms_loss_pl", "et_yolo_loss": "nms_loss_pl", "et_ota_assign": "nms_loss_pl", "et_score_log_append": "nms_loss_pl",
+        "et_select_targets": "nms_loss_pl", "et_yolo_loss": "nms_loss_pl", "et_ota_assign": "nms_loss_pl", "et_score_log_append": "nms_loss_pl", "et_pseudo_quality": "nms_loss_pl",
         "et_scale_cast": "nms_loss_pl", "et_domain_focal": "nms_loss_pl", "et_scale_inplace": "nms_loss_pl", "et_v8_decode": "nms_loss_pl",
         "et_tal_loss": "nms_loss_pl", "et_tal_assign": "nms_loss_pl", "et_colsum": "nms_loss_pl", "et_tal_pseudo_split": "nms_loss_pl", "et_tal_targets_pad": "nms_loss_pl",
         "et_tal_assigned_gt": "nms_loss_pl", "et_tal_merge_pseudo": "nms_loss_pl",
@@ -828,6 +828,39 @@ def pseudo_label_transform(dets, counts, M_s, width, height, clip01=False):
                                                      int(width), int(height), int(bool(clip01)), _lib.ptr(t9),
                                                      _lib.ptr(valid), _lib.stream(dets)), "et_pseudo_label_transform")
     return t9, valid
+
+
+def pseudo_label_quality(t9, valid, gt, thr_low, thr_high, batch_size, with_gt=True):
+    """the progress-bar numbers of trainer/ssod_trainer.py:655-672 from the PADDED pseudo-label table (csrc/pseudo_quality.hip):
+    t9 (N,9) fp64 + valid (N) uint8 as ``pseudo_label_transform`` returns them, gt (M,6) [img, cls, x, y, w, h] normalised (any row
+    order, M == 0 is legal, not modified; ignored when with_gt is false), thr_low / thr_high (nc) fp64 device tensors
+    -> (5,) fp64 on the device: [tp, fp_cls, fp_loc, pse_num, gt_num].  with_gt: check_pseudo_label_with_gt
+    (utils/self_supervised_utils.py:481-585); otherwise check_pseudo_label (:587-609).  Stream-ordered, no host synchronisation."""
+    import ctypes
+    dev = t9.device
+    N = t9.shape[0]
+    assert t9.dtype == torch.float64 and t9.dim() == 2 and t9.shape[1] == 9 and t9.is_contiguous()
+    assert valid.dtype == torch.uint8 and valid.numel() == N and valid.is_contiguous()
+    assert thr_low.dtype == thr_high.dtype == torch.float64 and thr_low.numel() == thr_high.numel() > 0
+    assert thr_low.is_contiguous() and thr_high.is_contiguous() and int(batch_size) > 0
+    _lib.ptr(t9)                          # a CPU tensor is refused before anything else happens
+    if N == 0:                            # no pseudo-label slot at all: the reference's invalid_target_shape zeros
+        return torch.zeros(5, dtype=torch.float64, device=dev)
+    out = torch.empty(5, dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    ws, M = None, 0
+    if with_gt:
+        gt = gt.reshape(-1, 6)
+        if gt.dtype != torch.float32 or not gt.is_contiguous() or gt.device != dev:
+            gt = gt.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()   # loader labels may still be on the host
+        M = gt.shape[0]
+        nbytes = ctypes.c_size_t()
+        _lib.check(lib.et_pseudo_quality_workspace_bytes(M, ctypes.byref(nbytes)), "et_pseudo_quality_workspace_bytes")
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    _lib.check(lib.et_pseudo_quality(_lib.ptr(t9), _lib.ptr(valid), N, _lib.ptr(gt) if M else None, M, _lib.ptr(thr_low),
+                                     _lib.ptr(thr_high), thr_low.numel(), int(batch_size), int(bool(with_gt)), _lib.ptr(ws),
+                                     _lib.ptr(out), _lib.stream(t9)), "et_pseudo_quality")
+    return out
 
 
 def strong_view_u8(weak, minv, lut, cutouts, flags, border_value=114):

@@ -329,34 +329,17 @@ class _SsodHotPath(_HotPath):
         return items
 
     def _pseudo_label_hit_rate(self, unlabeled_gt):
-        """the progress-bar statistics of ssod_trainer.py:657-673 (tp / fp_cls / fp_loc / pse_num / gt_num).  Without ground truth
-        (ssod_hyp.with_gt False, the recipes' setting) they are counts of reliable / uncertain pseudo labels
-        (utils/self_supervised_utils.py:587-609): computed on the device from the padded pseudo-label table; the reference's
-        meter reads them back with .item(), as it does for the loss items.  With ground truth the reference's own matching
-        routine runs on the compacted rows (logging code, host side in the reference too)."""
+        """the progress-bar statistics of ssod_trainer.py:657-673 (tp / fp_cls / fp_loc / pse_num / gt_num), on the device from the
+        padded pseudo-label table.  With ground truth (ssod_hyp.with_gt True: the coco-standard and cityscapes recipes) they say
+        how many of the uncertain pseudo labels hit a label of ``unlabeled_gt`` (utils/self_supervised_utils.py:481-585); without
+        (the voc and custom recipes) they are counts of reliable / uncertain pseudo labels (:587-609).  Either way one call of
+        this package's ``pseudo_label_hit_rate``: five 0-dim device tensors and no synchronisation here; the reference's meter
+        reads them back itself (utils/metrics.py:400), as it does for the loss items."""
+        from ..utils.self_supervised_utils import pseudo_label_hit_rate
         t9, valid = self._last_pseudo
-        lo = torch.as_tensor(self.compute_un_sup_loss.ignore_thres_low, dtype=torch.float64, device=t9.device)
-        hi = torch.as_tensor(self.compute_un_sup_loss.ignore_thres_high, dtype=torch.float64, device=t9.device)
-        v = valid.bool()
-        bs = self.batch_size // self.WORLD_SIZE
-        if getattr(self, "target_with_gt", False):
-            if not bool(v.any()):
-                return dict(tp=0, fp_cls=0, fp_loc=0, pse_num=0, gt_num=0)
-            from utils.self_supervised_utils import check_pseudo_label_with_gt          # the user's tree
-            tp, fp_cls, fp_loc, pse, gt = check_pseudo_label_with_gt(
-                t9[v].float().cpu(), unlabeled_gt.cpu(), ignore_thres_low=lo.tolist(), ignore_thres_high=hi.tolist(), batch_size=bs)
-            return dict(tp=tp, fp_cls=fp_cls, fp_loc=fp_loc, pse_num=pse, gt_num=gt)
-        cls = t9[:, 1].long().clamp_(0, lo.numel() - 1)
-        conf = t9[:, 6]
-        reliable = (v & (conf >= hi[cls])).sum().double() / bs
-        uncertain = (v & (conf < hi[cls]) & (conf >= lo[cls])).sum().double() / bs
-        n = v.sum().double()
-        both = reliable + uncertain
-        zero = torch.zeros((), dtype=torch.float64, device=t9.device)
-        tp = torch.where(both > 0, reliable / both.clamp_min(1e-300), zero)
-        recall = torch.where(n > 0, both * bs / n.clamp_min(1.0), zero)
-        # no pseudo label at all: the reference logs zeros (:657-659); the formulas above give zeros there too
-        return dict(tp=tp, fp_cls=0, fp_loc=recall, pse_num=both, gt_num=reliable)
+        thr = self.compute_un_sup_loss.refresh_thresholds(t9.device)
+        return pseudo_label_hit_rate(t9, valid, unlabeled_gt, thr[0], thr[1], self.batch_size // self.WORLD_SIZE,
+                                     bool(getattr(self, "target_with_gt", False)))
 
     def _side_stream(self):
         if self._side is None:

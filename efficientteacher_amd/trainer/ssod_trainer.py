@@ -56,6 +56,8 @@ class SSODTrainer(Trainer):
         self.da_loss_weights = cfg.SSOD.da_loss_weights
         self.cosine_ema = cfg.SSOD.cosine_ema
         self.fixed_accumulate = cfg.SSOD.fixed_accumulate
+        self.target_with_gt = bool(cfg.SSOD.ssod_hyp.with_gt)      # ssod_trainer.py:79
+        self._last_pseudo = None
         self.extra_teacher_models = []
         self.teacher_pred_hook = None      # optional callable(teacher_pred) -> teacher_pred (bench: synthetic scores)
         self.overlap_teacher = True        # teacher forward + pseudo labels on a second stream
@@ -282,6 +284,22 @@ class SSODTrainer(Trainer):
         self.update_optimizer(loss, ni)
         self._last_pseudo = (t9, valid)               # for the adapters' progress-bar statistics (ssod_trainer.py:657-673)
         return dict(sup_loss_items, **un_sup_loss_items)
+
+    def pseudo_label_hit_rate(self, unlabeled_gt=None, with_gt=None):
+        """the progress-bar statistics of the reference's ssod_trainer.py:655-672 for the last step's pseudo labels: a dict of
+        five 0-dim fp64 device tensors tp / fp_cls / fp_loc / pse_num / gt_num (utils/self_supervised_utils.py::
+        pseudo_label_hit_rate).  with_gt (default: the recipe's SSOD.ssod_hyp.with_gt) matches the uncertain pseudo labels against
+        ``unlabeled_gt`` (M,6) [img, cls, x, y, w, h], the unlabeled loader's targets; without it the numbers are the reliable /
+        uncertain counts.  Launches only: reading the tensors back is the caller's synchronisation."""
+        from ..utils.self_supervised_utils import pseudo_label_hit_rate
+        if getattr(self, "_last_pseudo", None) is None:
+            raise RuntimeError("pseudo_label_hit_rate: no train_instance has run yet")
+        with_gt = self.target_with_gt if with_gt is None else bool(with_gt)
+        if with_gt and unlabeled_gt is None:
+            raise ValueError("pseudo_label_hit_rate(with_gt=True) needs the unlabeled batch's ground truth")
+        t9, valid = self._last_pseudo
+        thr = self.compute_un_sup_loss.refresh_thresholds(t9.device)
+        return pseudo_label_hit_rate(t9, valid, unlabeled_gt, thr[0], thr[1], self.batch_size // max(self.WORLD_SIZE, 1), with_gt)
 
     def train_with_unlabeled(self, labeled_batches, unlabeled_batches, start_ni=0):
         """ssod_trainer.py:682-697 for iterables of the reference's batch tuples

@@ -31,7 +31,7 @@ enum { ET_F32 = 0, ET_BF16 = 1, ET_F16 = 2 };   /* ET_F16 (r05): IEEE half stora
  * for ("gfx950") and the ABI version.  ET_ABI_VERSION changes whenever an entry point is added or a signature / workspace
  * contract changes; a binding must refuse a library whose et_abi_version() differs from the header it was written against
  * (efficientteacher_amd/_lib.py does): a stale libet_hip.so would otherwise read e.g. a new int argument as the stream. */
-#define ET_ABI_VERSION 9
+#define ET_ABI_VERSION 10
 const char* et_build_arch(void);
 int et_abi_version(void);
 
@@ -410,6 +410,34 @@ int et_pseudo_label_transform(const float* dets, const int* counts, const double
  * beyond `cap` are dropped (the host checks the counter at the end of the epoch).                                       */
 int et_score_log_append(const float* dets, const int* counts, int B, int max_det, float* conf_log, int* cls_log,
                         uint64_t* log_count, int64_t cap, et_stream_t stream);
+
+/* Pseudo-label hit rate (csrc/pseudo_quality.hip): the progress-bar numbers tp / fp_cls / fp_loc / pse_num / gt_num of
+ * trainer/ssod_trainer.py:655-672, from the PADDED table above, with no host round trip.
+ * with_gt != 0 replaces check_pseudo_label_with_gt (utils/self_supervised_utils.py:481-585, iouv = [0.5]) with its
+ * select_targets (:456-479), xywh2xyxy (utils/general.py:630) and box_iou (utils/metrics.py:252-274):
+ *   targets9 (N, 9) fp64 + valid (N) uint8 as et_pseudo_label_transform writes them; gt (M, 6) fp32 rows
+ *   [img, cls, x, y, w, h], normalised, any row order (read only: the reference's in-place `gt *= 640` is not reproduced);
+ *   thr_low / thr_high (nc) fp64 DEVICE, the arrays et_select_targets takes.
+ *   1. a row takes part only if valid and UNCERTAIN: thr_low[cls] <= conf < thr_high[cls], compared in fp64 (reliable rows
+ *      are dropped: the reference overwrites `detections` with uc_pseudo at :504); n_unc = their number;
+ *   2. from there on fp32: boxes = xywh * 640, xywh2xyxy, + img * 640 on all four coordinates (640 is the reference's
+ *      literal at :515-518, not the image size); IoU in box_iou's operation order;
+ *   3. pairs (label, pseudo) of the same image fall into  tp: iou >= 0.5, same class;  fp_cls: iou >= 0.5, other class;
+ *      fp_loc: 0.01 < iou < 0.5, any class;
+ *   4. per category every pseudo row picks its qualifying label of largest IoU; the count is the number of DISTINCT labels
+ *      picked (what the argsort / np.unique on the detection / np.unique on the label of :544-566 leaves).  Equal IoU: the
+ *      LOWER label index; the reference leaves that to an unstable sort;
+ *   out5 fp64 DEVICE = [tp / n_unc, fp_cls / n_unc, fp_loc / n_unc (0 when n_unc == 0), n_unc / batch_size, M / batch_size];
+ *   all five 0 when no row is valid at all (invalid_target_shape, ssod_trainer.py:658-660).
+ * with_gt == 0 replaces check_pseudo_label (:587-609) as ssod_trainer.py:667-671 logs it: with reliable (conf >= thr_high[cls])
+ * and uncertain counts divided by batch_size, out5 = [reliable / (reliable + uncertain), 0, (reliable + uncertain) *
+ * batch_size / n_valid, reliable + uncertain, reliable]; gt / M / workspace are not read.
+ * workspace: et_pseudo_quality_workspace_bytes(M) bytes ((3, M) byte flags), cleared on the stream by the call itself.
+ * Integer counts and one fp64 division per number: deterministic.  M == 0 is legal; N > 0. */
+int et_pseudo_quality_workspace_bytes(int M, size_t* bytes /*host out*/);
+int et_pseudo_quality(const double* targets9, const uint8_t* valid, int N, const float* gt, int M, const double* thr_low,
+                      const double* thr_high, int nc, int batch_size, int with_gt, void* workspace, double* out5,
+                      et_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Detection losses with fused anchor assignment, forward + gradient.  Replaces
