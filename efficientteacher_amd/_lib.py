@@ -84,6 +84,9 @@ SIGNATURES = {
     "et_score_log_append": (c_int, [P, P, c_int, c_int, P, P, P, c_int64, P]),
     "et_pseudo_quality_workspace_bytes": (c_int, [c_int, ctypes.POINTER(c_size_t)]),
     "et_pseudo_quality": (c_int, [P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, P, P]),
+    "et_labelmatch_thresholds_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
+    "et_labelmatch_thresholds": (c_int, [P, P, P, c_int64, c_int, c_int, c_double, c_double, c_double, P, P, P, P, P, P, P, P, P,
+                                         P, c_size_t, P]),
     "et_yolo_loss": (c_int, [P, P]),
     "et_ota_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "et_ota_assign": (c_int, [P, P, c_float, c_int, P, P, P]),
@@ -130,7 +133,7 @@ CALL_TIMER = None
 _NO_LAUNCH = frozenset(n for n in (
     "et_build_arch", "et_abi_version", "et_nms_ssod_workspace_bytes", "et_nms_workspace_bytes", "et_conv2d_stats_rows", "et_conv2d_stats_rows_for",
     "et_conv2d_kernel_name", "et_conv2d_stem_kernel_name", "et_env_knobs", "et_bn_reduce_rows", "et_ota_workspace_bytes", "et_tal_assign_workspace_bytes", "et_val_ap_workspace_bytes",
-    "et_pseudo_quality_workspace_bytes"))
+    "et_pseudo_quality_workspace_bytes", "et_labelmatch_thresholds_workspace_bytes"))
 
 
 class _TimedDll:

@@ -16,7 +16,7 @@ ARCH = "gfx950"
 
 # exact-rounding files: integer/index decisions depend on fp32 results, so no FMA contraction
 EXACT = {"nms.hip", "loss.hip", "pseudo_label.hip", "detect.hip", "optim.hip", "tal.hip", "augment.hip", "metrics.hip",
-         "pseudo_quality.hip"}
+         "pseudo_quality.hip", "labelmatch.hip"}
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I", os.path.join(ROOT, "include")]
 

@@ -51,7 +51,7 @@ class FamilyTimer:
         "et_conv2d_wgrad": "wgrad", "et_conv2d_wgrad_grouped": "wgrad", "et_conv2d_stem_u8_fwd": "gather_gemm", "et_conv2d_stem_u8_wgrad": "wgrad",
         "et_bn_finalize": "bn", "et_bn_act_fwd": "bn", "et_bn_act_fwd_sharded": "bn", "et_bn_act_bwd_sharded": "bn", "et_bn_act_bwd": "bn", "et_bn_act_bwd_from_partials": "bn", "et_act_bwd": "bn",
         "et_nms": "nms_loss_pl", "et_nms_ssod": "nms_loss_pl", "et_detect_decode": "nms_loss_pl", "et_pseudo_label_transform": "nms_loss_pl",
-        "et_select_targets": "nms_loss_pl", "et_yolo_loss": "nms_loss_pl", "et_ota_assign": "nms_loss_pl", "et_score_log_append": "nms_loss_pl", "et_pseudo_quality": "nms_loss_pl",
+        "et_select_targets": "nms_loss_pl", "et_yolo_loss": "nms_loss_pl", "et_ota_assign": "nms_loss_pl", "et_score_log_append": "nms_loss_pl", "et_labelmatch_thresholds": "nms_loss_pl", "et_pseudo_quality": "nms_loss_pl",
         "et_scale_cast": "nms_loss_pl", "et_domain_focal": "nms_loss_pl", "et_scale_inplace": "nms_loss_pl", "et_v8_decode": "nms_loss_pl",
         "et_tal_loss": "nms_loss_pl", "et_tal_assign": "nms_loss_pl", "et_colsum": "nms_loss_pl", "et_tal_pseudo_split": "nms_loss_pl", "et_tal_targets_pad": "nms_loss_pl",
         "et_tal_assigned_gt": "nms_loss_pl", "et_tal_merge_pseudo": "nms_loss_pl",
@@ -884,6 +884,68 @@ def score_log_append(dets, counts, conf_log, cls_log, log_count):
     _lib.check(_lib.load().et_score_log_append(_lib.ptr(dets), _lib.ptr(counts), B, max_det, _lib.ptr(conf_log),
                                                _lib.ptr(cls_log), _lib.ptr(log_count), conf_log.numel(),
                                                _lib.stream(dets)), "et_score_log_append")
+
+
+LM_OK, LM_RANK_OUT_OF_SEGMENT = 0, 1      # status codes of et_labelmatch_thresholds (include/et_hip.h)
+
+
+class LabelMatchThresholds:
+    """what ``labelmatch_thresholds`` leaves on the device: ONE packed fp64 buffer (``packed``) and typed views into it --
+    thr_high / thr_low (nc) fp64, n_per_class / cls_num_total (nc) int64, gmm (nc, 6) fp64, log_count (1) int64 (the raw counter,
+    not clamped to the capacity), n_iter / status (nc) int32 -- plus sorted_conf (cap) fp32 and seg_offset (nc + 1) int64 when
+    they were asked for.  ``host()`` is the one read: a dict of numpy arrays from a single device-to-host copy."""
+
+    def __init__(self, nc, device):
+        self.nc = nc
+        half = (nc + 1) // 2                                   # nc int32 in fp64 slots
+        self.packed = torch.zeros(10 * nc + 1 + 2 * half, dtype=torch.float64, device=device)
+        self.sorted_conf = self.seg_offset = None
+        for name, view in self._views(self.packed).items():
+            setattr(self, name, view)
+
+    def _views(self, packed):
+        nc, half = self.nc, (self.nc + 1) // 2
+        i64, i32 = packed.view(torch.int64), packed.view(torch.int32)
+        b = 10 * nc + 1
+        return dict(thr_high=packed[0:nc], thr_low=packed[nc:2 * nc], n_per_class=i64[2 * nc:3 * nc], cls_num_total=i64[3 * nc:4 * nc],
+                    gmm=packed[4 * nc:10 * nc].view(nc, 6), log_count=i64[10 * nc:b], n_iter=i32[2 * b:2 * b + nc],
+                    status=i32[2 * (b + half):2 * (b + half) + nc])
+
+    def host(self):
+        return {k: v.numpy() for k, v in self._views(self.packed.cpu()).items()}
+
+
+def labelmatch_thresholds(conf_log, cls_log, log_count, nc, epoch, ignore_thres_low, ignore_thres_high, resample_low_percent,
+                          cls_num_total, want_sorted=False):
+    """LabelMatch.update_epoch_cls_thr (utils/labelmatch.py:188-240, gmm_policy :138-189) from the device score log
+    (csrc/labelmatch.hip): conf_log (cap) fp32, cls_log (cap) int32, log_count (1) int64 as ``score_log_append`` fills them;
+    cls_num_total (nc) int64 on the device, the running per-class total BEFORE this epoch (not modified: the new total is in the
+    result).  -> LabelMatchThresholds.  Stream-ordered, no host synchronisation; an overflown log is the caller's to refuse (the
+    result carries the raw counter)."""
+    import ctypes
+    dev = conf_log.device
+    cap = conf_log.numel()
+    assert conf_log.dtype == torch.float32 and cls_log.dtype == torch.int32 and log_count.dtype == torch.int64
+    assert cls_log.numel() == cap and log_count.numel() == 1 and conf_log.is_contiguous() and cls_log.is_contiguous()
+    assert cls_num_total.dtype == torch.int64 and cls_num_total.numel() == nc and int(epoch) >= 0
+    lib = _lib.load()
+    _lib.ptr(conf_log)                        # a CPU tensor is refused before anything else happens
+    out = LabelMatchThresholds(int(nc), dev)
+    out.cls_num_total.copy_(cls_num_total)
+    out.log_count.copy_(log_count)
+    if want_sorted:
+        out.sorted_conf = torch.empty(cap, dtype=torch.float32, device=dev)
+        out.seg_offset = torch.empty(nc + 1, dtype=torch.int64, device=dev)
+    nbytes = ctypes.c_size_t()
+    _lib.check(lib.et_labelmatch_thresholds_workspace_bytes(cap, int(nc), ctypes.byref(nbytes)), "et_labelmatch_thresholds_workspace_bytes")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    _lib.check(lib.et_labelmatch_thresholds(_lib.ptr(conf_log), _lib.ptr(cls_log), _lib.ptr(log_count), cap, int(nc), int(epoch),
+                                            float(ignore_thres_low), float(ignore_thres_high), float(resample_low_percent),
+                                            _lib.ptr(out.cls_num_total), _lib.ptr(out.thr_high), _lib.ptr(out.thr_low),
+                                            _lib.ptr(out.n_per_class), _lib.ptr(out.n_iter), _lib.ptr(out.status), _lib.ptr(out.gmm),
+                                            _lib.ptr(out.sorted_conf), _lib.ptr(out.seg_offset), _lib.ptr(ws), nbytes.value,
+                                            _lib.stream(conf_log)), "et_labelmatch_thresholds")
+    return out
 
 
 def val_match(dets, counts, targets, shapes, net_hw, iouv, nc, correct, conf, cls, valid, nt, row_offset=0, single_cls=False):

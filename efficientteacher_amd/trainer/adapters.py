@@ -120,6 +120,8 @@ class _HotPath:
     ET_DETERMINISTIC = False
     # hot_path_trainers(device_val=True): end-of-epoch validation through this package's val.run instead of the reference's
     ET_DEVICE_VAL = False
+    # hot_path_trainers(device_labelmatch=True): LabelMatch's end-of-epoch thresholds from the device log (csrc/labelmatch.hip)
+    ET_DEVICE_LABELMATCH = False
 
     def _et_val(self, val):
         return DeviceVal(val) if (self.ET_DEVICE_VAL and val is not None and not isinstance(val, DeviceVal)) else val
@@ -281,7 +283,7 @@ class _SsodHotPath(_HotPath):
         elif cfg.SSOD.pseudo_label_type == 'LabelMatch':          # ssod_trainer.py:70-71; after_epoch (:320-323) drives it unchanged
             from ..utils.labelmatch import LabelMatch
             self.pseudo_label_creator = LabelMatch(cfg, int(len(self.unlabeled_dataset) / self.WORLD_SIZE), self.label_num_per_image,
-                                                   cls_ratio_gt=self.cls_ratio_gt)
+                                                   cls_ratio_gt=self.cls_ratio_gt, device_thresholds=self.ET_DEVICE_LABELMATCH)
         else:
             raise NotImplementedError(f"SSOD.pseudo_label_type {cfg.SSOD.pseudo_label_type}")
 
@@ -378,14 +380,17 @@ class DeviceVal:
                           names=names or data.get("names"), eval_num=eval_num, verbose=verbose)
 
 
-def hot_path_trainers(ref_trainer=None, ref_ssod_trainer=None, compute_dtype=torch.bfloat16, deterministic=False, device_val=False):
+def hot_path_trainers(ref_trainer=None, ref_ssod_trainer=None, compute_dtype=torch.bfloat16, deterministic=False, device_val=False,
+                      device_labelmatch=False):
     """(Trainer, SSODTrainer): subclasses of the reference's trainers -- taken from the tree this is called in
     (``trainer.trainer.Trainer`` / ``trainer.ssod_trainer.SSODTrainer``) unless passed explicitly.
     compute_dtype: torch.bfloat16 (default: no loss scaling), torch.float16 (the reference's autocast dtype; ``self.scaler`` is then
     the device-resident GradScaler the reference's ``update_optimizer`` drives unchanged) or torch.float32 (parity mode).
     deterministic: BatchNorm statistics of the 16-bit modes on the reproducible partial-row path (FlatState(deterministic=True)).
     device_val: off by default (validation stays the reference's val.run); True routes the trainers' end-of-epoch ``val.run`` calls
-    through this package's device-resident ``val.run`` (``DeviceVal`` wraps the ``val`` module train.py passes in)."""
+    through this package's device-resident ``val.run`` (``DeviceVal`` wraps the ``val`` module train.py passes in).
+    device_labelmatch: off by default (LabelMatch's end-of-epoch thresholds stay the reference's host arithmetic with sklearn); True
+    computes them on the device (``LabelMatch(device_thresholds=True)``, csrc/labelmatch.hip)."""
     if compute_dtype not in (torch.bfloat16, torch.float16, torch.float32):
         raise ValueError(f"compute_dtype {compute_dtype}")
     if ref_trainer is None or ref_ssod_trainer is None:
@@ -395,5 +400,6 @@ def hot_path_trainers(ref_trainer=None, ref_ssod_trainer=None, compute_dtype=tor
                                                       "ET_DETERMINISTIC": bool(deterministic), "ET_DEVICE_VAL": bool(device_val)})
     ssod = type("SSODTrainer", (_SsodHotPath, ref_ssod_trainer), {"__doc__": "reference SSODTrainer with the MI355X hot path",
                                                                    "ET_COMPUTE_DTYPE": compute_dtype, "ET_DETERMINISTIC": bool(deterministic),
-                                                                   "ET_DEVICE_VAL": bool(device_val)})
+                                                                   "ET_DEVICE_VAL": bool(device_val),
+                                                                   "ET_DEVICE_LABELMATCH": bool(device_labelmatch)})
     return hot, ssod

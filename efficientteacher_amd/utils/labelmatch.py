@@ -6,6 +6,10 @@ In the step (``create_pseudo_label_padded``): NMS -> append every detection's (c
 :333 -- no host synchronisation.  At the end of the epoch (``update_epoch_cls_thr``, :188-240): the log is read once, and
 per class the low threshold is the score at a fixed rank, the high threshold comes from a two-component Gaussian mixture
 (``gmm_policy``, :134-186; sklearn.mixture.GaussianMixture as in the reference).
+
+``LabelMatch(..., device_thresholds=True)`` keeps the end of the epoch on the device as well (``ops.labelmatch_thresholds``,
+csrc/labelmatch.hip): class sort, rank lookup and the mixture fit run as kernels on the log where it lies, one small packed
+result is read back, and sklearn is not imported.  Off by default: the host path above is the reference's own arithmetic.
 """
 import logging
 
@@ -19,7 +23,7 @@ LOGGER = logging.getLogger(__name__)
 
 
 class LabelMatch:
-    def __init__(self, cfg, target_data_len, label_num_per_img, cls_ratio_gt, score_log_capacity=None):
+    def __init__(self, cfg, target_data_len, label_num_per_img, cls_ratio_gt, score_log_capacity=None, device_thresholds=False):
         self.nc = int(np.asarray(cls_ratio_gt).shape[0])
         self.multi_label = cfg.SSOD.multi_label
         self.nms_conf_thres = cfg.SSOD.nms_conf_thres
@@ -47,6 +51,8 @@ class LabelMatch:
         self.capacity = int(score_log_capacity or max(1 << 16, 64 * int(target_data_len)))
         self._log = None
         self._cls_hist = None
+        self.device_thresholds = bool(device_thresholds)
+        self._sorted = None                 # device path: (sorted_conf, seg_offset) of the epoch that was closed last
 
     # -- per step -------------------------------------------------------------------------------------------------
     def _ensure_log(self, dev):
@@ -127,8 +133,63 @@ class LabelMatch:
             thr = float(scores[assign == 1].min())
         return max(given_gt_thr, thr)
 
+    def _overflow(self, n):
+        return RuntimeError(f"LabelMatch score log overflow: {n} detections this epoch, capacity {self.capacity}; "
+                            "construct LabelMatch with a larger score_log_capacity")
+
+    def closed_epoch_scores(self):
+        """device path: the per-class score lists (sorted descending) of the epoch ``update_epoch_cls_thr`` closed last, served from
+        the kernel's sorted log (host; one D2H copy)"""
+        lists = [[] for _ in range(self.nc)]
+        if self._sorted is None:
+            return lists
+        seg = self._sorted[1].cpu().numpy()
+        conf = self._sorted[0][:int(seg[-1])].cpu().numpy()
+        return [[float(v) for v in conf[seg[c]:seg[c + 1]]] for c in range(self.nc)]
+
+    def _update_epoch_cls_thr_device(self, epoch):
+        """:188-240 on the device: one call, one small read"""
+        if self._log is not None:
+            conf_log, cls_log, n_log = self._log
+            total = torch.from_numpy(self.cls_num_total.astype(np.int64)).to(conf_log.device)
+            res = ops.labelmatch_thresholds(conf_log, cls_log, n_log, self.nc, epoch, self.ignore_thres_low, self.ignore_thres_high,
+                                            self.resample_low_percent, total, want_sorted=True)
+            h = res.host()                                                       # the one synchronisation of the epoch's end
+            n = int(h["log_count"][0])
+            if n > self.capacity:
+                raise self._overflow(n)
+            self._sorted = (res.sorted_conf, res.seg_offset)
+            counts, high, low, status = h["n_per_class"], h["thr_high"], h["thr_low"], h["status"]
+            self.cls_num_total = h["cls_num_total"].astype(np.float64)
+        else:                                                                    # no step ran: every class is empty
+            counts, status = np.zeros(self.nc, np.int64), np.zeros(self.nc, np.int32)
+            high, low = np.full(self.nc, self.ignore_thres_high), np.full(self.nc, self.ignore_thres_low)
+        if self._cls_hist is not None:
+            self.cls_tmp = self._cls_hist.cpu().numpy().astype(np.float64)
+        for c in range(self.nc):
+            n_c = int(counts[c])
+            max_pseudo_label_num = int(self.cls_num_total[c] / (epoch + 1))
+            if n_c == 0:
+                pos_loc_high = pos_loc_low = -1
+            else:
+                pos_loc_high = int(n_c * self.resample_high_percent)
+                pos_loc_low = min(max_pseudo_label_num, int(n_c * self.resample_low_percent))
+            if int(status[c]) == ops.LM_RANK_OUT_OF_SEGMENT:                     # s[pos_loc_low] of the host path (:234)
+                raise IndexError(f"list index out of range: class {c} has {n_c} scores, pos_loc_low {pos_loc_low}")
+            self.cls_thr_high[c] = float(high[c])
+            self.cls_thr_low[c] = float(low[c])
+            LOGGER.info(f'{n_c} {max_pseudo_label_num} {pos_loc_high}:{self.cls_thr_high[c]} {pos_loc_low}:{self.cls_thr_low[c]}')
+        if self._log is not None:
+            self._log[2].zero_()
+        self._cls_hist = None
+        self.cls_tmp = np.zeros(self.nc)
+        self.count = 0
+        self.pse_count = 0
+
     def update_epoch_cls_thr(self, epoch):
         """:188-240"""
+        if self.device_thresholds:
+            return self._update_epoch_cls_thr_device(epoch)
         lists = self.epoch_scores()
         if self._cls_hist is not None:
             self.cls_tmp = self._cls_hist.cpu().numpy().astype(np.float64)

@@ -31,7 +31,7 @@ enum { ET_F32 = 0, ET_BF16 = 1, ET_F16 = 2 };   /* ET_F16 (r05): IEEE half stora
  * for ("gfx950") and the ABI version.  ET_ABI_VERSION changes whenever an entry point is added or a signature / workspace
  * contract changes; a binding must refuse a library whose et_abi_version() differs from the header it was written against
  * (efficientteacher_amd/_lib.py does): a stale libet_hip.so would otherwise read e.g. a new int argument as the stream. */
-#define ET_ABI_VERSION 10
+#define ET_ABI_VERSION 11
 const char* et_build_arch(void);
 int et_abi_version(void);
 
@@ -438,6 +438,31 @@ int et_pseudo_quality_workspace_bytes(int M, size_t* bytes /*host out*/);
 int et_pseudo_quality(const double* targets9, const uint8_t* valid, int N, const float* gt, int M, const double* thr_low,
                       const double* thr_high, int nc, int batch_size, int with_gt, void* workspace, double* out5,
                       et_stream_t stream);
+
+/* LabelMatch's end-of-epoch thresholds (csrc/labelmatch.hip): update_epoch_cls_thr (utils/labelmatch.py:188-240) with gmm_policy
+ * (:138-189, policy 'high', given_gt_thr 0.0) from the device log et_score_log_append fills, with no host synchronisation: the
+ * live count min(*log_count, cap) is read on the device (an overflow stays the caller's error: it reads *log_count itself).
+ *   conf_log / cls_log / log_count: the log; pairs whose class is outside [0, nc) are dropped; confidences are positive floats.
+ *   cls_num_total (nc) int64 DEVICE, in/out: += the class's count, as the reference's running total (:211).
+ *   thr_high / thr_low (nc) fp64: the reference's cls_thr_high / cls_thr_low; an empty class gets ignore_thres_high / _low; every
+ *     other value is one of the logged fp32 confidences, ignore_thres_low, or 0.0 (fewer than four scores, or nothing assigned to
+ *     the upper mixture component).
+ *   n_per_class (nc) int64; n_iter (nc) int: GaussianMixture's n_iter_ (0 where no mixture is fitted); gmm (nc, 6) fp64:
+ *     weights, means, variances of the two components (zeros where no mixture is fitted).
+ *   status (nc) int: ET_LM_OK, or ET_LM_RANK_OUT_OF_SEGMENT where pos_loc_low (:223) is not an index into the class's scores -- the
+ *     reference raises IndexError at :234; nothing is read there and thr_low[c] is ignore_thres_low.
+ *   sorted_conf (cap) fp32, optional: the scores ordered by (class ascending, confidence descending), zeros behind them;
+ *   seg_offset (nc + 1) int64, optional: class c's scores are sorted_conf[seg_offset[c] .. seg_offset[c + 1]).
+ *   ws: et_labelmatch_thresholds_workspace_bytes(cap, nc) bytes.  cap < 2^31, nc < 65535.
+ * Every output is a function of the multiset of logged pairs (no floating-point atomics): the append order does not matter. */
+enum { ET_LM_OK = 0, ET_LM_RANK_OUT_OF_SEGMENT = 1 };
+int et_labelmatch_thresholds_workspace_bytes(int64_t cap, int nc, size_t* bytes /*host out*/);
+int et_labelmatch_thresholds(const float* conf_log, const int* cls_log, const uint64_t* log_count, int64_t cap, int nc,
+                             int epoch, double ignore_thres_low, double ignore_thres_high, double resample_low_percent,
+                             int64_t* cls_num_total /* in/out, nc */, double* thr_high, double* thr_low /* nc each */,
+                             int64_t* n_per_class, int* n_iter, int* status /* nc each */, double* gmm /* nc x 6: w0 w1 mu0 mu1 var0 var1 */,
+                             float* sorted_conf /* optional, cap */, int64_t* seg_offset /* optional, nc+1 */,
+                             void* ws, size_t ws_bytes, et_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Detection losses with fused anchor assignment, forward + gradient.  Replaces
