@@ -72,12 +72,10 @@ struct GatherGeom {
     int tapinfo[CONV_MAX_TAPS];  // (dy & 0xff) | (dx & 0xff) << 8 | wt << 16 : one scalar load per chunk
 };
 
-enum { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2 };
-
 struct Epilogue {
     const float* scale;     // [Cout] or null: v = acc*scale (folded eval-mode BatchNorm)
     const float* bias;      // [Cout] or null
-    int act;
+    int act;                // ACT_* (et_host.h)
     const void* res;        // residual (same dtype, added after act) or null
     int ldr;
     float* stats;           // partial BN statistics [gridDim.x][2][Cout] or null

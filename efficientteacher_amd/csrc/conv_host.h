@@ -1,20 +1,13 @@
 // Host-only declarations shared by the conv host layer (conv_host.hip) and the kernel files, whose launch functions it calls.
+// The dtype / activation dispatch (with_dtype, with_act) is et_host.h's, shared with the kernel files outside the conv family.
 #pragma once
+#include "et_host.h"
 #include "conv_device.h"
 
 static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static int device_cus() {
     static const int n_cu = [] { hipDeviceProp_t p; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }();
     return n_cu;
-}
-
-// f(TypeTag<T>) for the storage type of an ET_* dtype; -2 for any other value (the launch functions: all three types)
-template <typename T> struct TypeTag { using type = T; };
-template <typename F> static int with_dtype(int dtype, F&& f) {
-    if (dtype == ET_F32) return f(TypeTag<float>{});
-    if (dtype == ET_BF16) return f(TypeTag<uint16_t>{});
-    if (dtype == ET_F16) return f(TypeTag<et_f16>{});
-    return -2;
 }
 
 enum { GEMM_REG = 0, GEMM_GLDS = 1, GEMM_PP = 2, GEMM_RS = 3, GEMM_PPRS = 4, GEMM_S1 = 5 };

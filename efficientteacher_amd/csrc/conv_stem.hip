@@ -461,17 +461,22 @@ void launch_stem(bool u8, StemArgs& a, int dtype, const float* scale, const floa
     a.stat_rows = (a.N * a.OH * a.OW + 63) / 64;        // == et_conv2d_stats_rows
     int grid = stem_grid(a.ntiles);
     if (stats && !stats_ld && grid > a.stat_rows) grid = a.stat_rows;
-#define ET_STEM(T_, ACT_) \
-    do { \
-        if (u8) hipLaunchKernelGGL((conv_stem_u8_kernel<T_, ACT_>), dim3(grid), dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL((conv_stem_kernel<T_, ACT_>), dim3(grid), dim3(256), 0, s, a); \
-    } while (0)
-    if (dtype == ET_F16) { if (act == ACT_SILU) ET_STEM(et_f16, ACT_SILU); else if (act == ACT_RELU) ET_STEM(et_f16, ACT_RELU); else ET_STEM(et_f16, ACT_NONE); }
-    else { if (act == ACT_SILU) ET_STEM(uint16_t, ACT_SILU); else if (act == ACT_RELU) ET_STEM(uint16_t, ACT_RELU); else ET_STEM(uint16_t, ACT_NONE); }
-#undef ET_STEM
+    (void)with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if constexpr (et_is_lp<T>::value)              // the stem kernels exist for the 16-bit types only: the callers have checked (stem_eligible, stem_u8_mode)
+            with_act(act, [&](auto ac) {
+                constexpr int ACT = decltype(ac)::value;
+                if (u8) hipLaunchKernelGGL((conv_stem_u8_kernel<T, ACT>), dim3(grid), dim3(256), 0, s, a);
+                else hipLaunchKernelGGL((conv_stem_kernel<T, ACT>), dim3(grid), dim3(256), 0, s, a);
+            });
+        return 0;
+    });
 }
 
 void launch_stem_u8_wgrad(const StemWgradArgs& a, int dtype, int grid, hipStream_t s) {
-    if (dtype == ET_F16) hipLaunchKernelGGL((conv_stem_u8_wgrad_kernel<et_f16>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((conv_stem_u8_wgrad_kernel<uint16_t>), dim3(grid), dim3(256), 0, s, a);
+    (void)with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if constexpr (et_is_lp<T>::value) hipLaunchKernelGGL((conv_stem_u8_wgrad_kernel<T>), dim3(grid), dim3(256), 0, s, a);   // 16-bit only, as launch_stem
+        return 0;
+    });
 }

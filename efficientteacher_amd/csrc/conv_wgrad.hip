@@ -776,61 +776,54 @@ int launch_wgrad_row(const WgradRow* wp, int dtype, const WgradGroup& grp, const
     });
 }
 
+// the transposes move words: the two 16-bit formats share the uint16_t instantiation
+template <typename T> using word_t = std::conditional_t<sizeof(T) == 2, uint16_t, float>;
+
 extern "C" int et_weight_transpose(const void* w, void* wT, int dtype, int Cout, int taps, int Cin, et_stream_t stream) {
     if (!w || !wT) return -1;
     const long long n = (long long)Cout * taps * Cin;
     if (n <= 0) return -2;
-    const dim3 grid(et_cdiv(n, 256)), block(256);
-    if (dtype == ET_F32)
-        hipLaunchKernelGGL((weight_transpose_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)w, (float*)wT, Cout, taps, Cin, n);
-    else if (dtype == ET_BF16 || dtype == ET_F16)       // moves 16-bit words: format-agnostic
-        hipLaunchKernelGGL((weight_transpose_kernel<uint16_t>), grid, block, 0, (hipStream_t)stream, (const uint16_t*)w, (uint16_t*)wT, Cout, taps, Cin, n);
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = word_t<typename decltype(t)::type>;
+        hipLaunchKernelGGL((weight_transpose_kernel<T>), dim3(et_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)w, (T*)wT, Cout, taps, Cin, n);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_weight_transpose_all(const void* w_arena, void* wT_arena, int dtype, const int* table, int n_layers,
                                        long long total_elems, et_stream_t stream) {
     if (!w_arena || !wT_arena || !table) return -1;
     if (n_layers <= 0 || total_elems <= 0) return -2;
-    const dim3 grid(et_cdiv(total_elems, 256)), block(256);
-    if (dtype == ET_F32)
-        hipLaunchKernelGGL((weight_transpose_all_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)w_arena,
-                           (float*)wT_arena, table, n_layers, total_elems);
-    else if (dtype == ET_BF16 || dtype == ET_F16) {
+    return with_dtype(dtype, [&](auto t) {
+        using T = word_t<typename decltype(t)::type>;
         // layer offsets are multiples of 16 elements and 16-bit channel counts multiples of 8 (flat_state.py): 16-byte rows (a layer
         // whose channels are not is copied element by element inside the same launch)
-        if ((((uintptr_t)w_arena | (uintptr_t)wT_arena) & 15) == 0)
-            hipLaunchKernelGGL(weight_transpose_all_tiled_kernel, dim3(96, n_layers), block, 0, (hipStream_t)stream,
+        if (sizeof(T) == 2 && (((uintptr_t)w_arena | (uintptr_t)wT_arena) & 15) == 0)
+            hipLaunchKernelGGL(weight_transpose_all_tiled_kernel, dim3(96, n_layers), dim3(256), 0, (hipStream_t)stream,
                                (const uint16_t*)w_arena, (uint16_t*)wT_arena, table, n_layers);
         else
-            hipLaunchKernelGGL((weight_transpose_all_kernel<uint16_t>), grid, block, 0, (hipStream_t)stream,
-                               (const uint16_t*)w_arena, (uint16_t*)wT_arena, table, n_layers, total_elems);
-    } else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+            hipLaunchKernelGGL((weight_transpose_all_kernel<T>), dim3(et_cdiv(total_elems, 256)), dim3(256), 0, (hipStream_t)stream,
+                               (const T*)w_arena, (T*)wT_arena, table, n_layers, total_elems);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_colsum(const void* x, int dtype, int P, int C, int ld, float* out, et_stream_t stream) {
     if (!x || !out) return -1;
     if (P <= 0 || C <= 0) return -2;
-    const int rpb = 256;
-    const dim3 grid((C + 255) / 256, (P + rpb - 1) / rpb), block(256);
-    if (dtype == ET_F32) hipLaunchKernelGGL((colsum_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)x, P, C, ld, rpb, out);
-    else if (dtype == ET_BF16 || dtype == ET_F16) {
+    const int rpb = 256;                                       // rows per block (vec8: 8-256 rows per row group, two in flight per thread)
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
         const int CV = C / 8;
-        const bool vec8 = C % 8 == 0 && ld % 8 == 0 && CV >= 1 && CV <= 256 && 256 % CV == 0 && (((uintptr_t)x) & 15) == 0;
-        const int rpb2 = 256;                                  // rows per block: 8-256 rows per row group, two in flight per thread
-        if (dtype == ET_BF16) {
-            if (vec8) hipLaunchKernelGGL((colsum_vec8_kernel<uint16_t>), dim3((P + rpb2 - 1) / rpb2), block, 0, (hipStream_t)stream, (const uint16_t*)x, P, CV, ld, rpb2, out);
-            else hipLaunchKernelGGL((colsum_kernel<uint16_t>), grid, block, 0, (hipStream_t)stream, (const uint16_t*)x, P, C, ld, rpb, out);
-        } else {
-            if (vec8) hipLaunchKernelGGL((colsum_vec8_kernel<et_f16>), dim3((P + rpb2 - 1) / rpb2), block, 0, (hipStream_t)stream, (const et_f16*)x, P, CV, ld, rpb2, out);
-            else hipLaunchKernelGGL((colsum_kernel<et_f16>), grid, block, 0, (hipStream_t)stream, (const et_f16*)x, P, C, ld, rpb, out);
+        const bool vec8 = et_is_lp<T>::value && C % 8 == 0 && ld % 8 == 0 && CV >= 1 && CV <= 256 && 256 % CV == 0 && (((uintptr_t)x) & 15) == 0;
+        if constexpr (et_is_lp<T>::value) {            // colsum_vec8_kernel: 16-bit inputs only
+            if (vec8) hipLaunchKernelGGL((colsum_vec8_kernel<T>), dim3((P + rpb - 1) / rpb), dim3(256), 0, (hipStream_t)stream, (const T*)x, P, CV, ld, rpb, out);
         }
-    }
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+        if (!vec8)
+            hipLaunchKernelGGL((colsum_kernel<T>), dim3((C + 255) / 256, (P + rpb - 1) / rpb), dim3(256), 0, (hipStream_t)stream, (const T*)x, P, C, ld, rpb, out);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }

@@ -4,8 +4,7 @@
 // (B, na, ny, nx, no); no permute/contiguous copy is materialised) and writes this level's slice of
 // z (B, A_total, no) fp32.  HBM-bound elementwise kernel: one workgroup per (b, a, y) output row,
 // lanes run over the contiguous x*no + c axis.
-#include "et_device.h"
-#include "../../include/et_hip.h"
+#include "et_host.h"
 
 template <typename T>
 __global__ __launch_bounds__(256) void detect_decode_kernel(const T* __restrict__ raw, int na, int ny, int nx, int no,
@@ -40,22 +39,12 @@ extern "C" int et_detect_decode(const void* raw, int dtype, int B, int na, int n
                                 float stride, float* z, int64_t A_total, int64_t a_offset, et_stream_t stream) {
     if (!raw || !anchor_px || !z) return -1;
     if (B <= 0 || na <= 0 || ny <= 0 || nx <= 0 || no < 5) return -2;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(B * na * ny), block(256);
-    if (dtype == ET_F32)
-        hipLaunchKernelGGL((detect_decode_kernel<float>), grid, block, 0, s, (const float*)raw, na, ny, nx, no,
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((detect_decode_kernel<T>), dim3(B * na * ny), dim3(256), 0, (hipStream_t)stream, (const T*)raw, na, ny, nx, no,
                            (long long)sb, (long long)sa, (long long)sy, (long long)sx, anchor_px, stride, z,
                            (long long)A_total, (long long)a_offset);
-    else if (dtype == ET_BF16)
-        hipLaunchKernelGGL((detect_decode_kernel<uint16_t>), grid, block, 0, s, (const uint16_t*)raw, na, ny, nx, no,
-                           (long long)sb, (long long)sa, (long long)sy, (long long)sx, anchor_px, stride, z,
-                           (long long)A_total, (long long)a_offset);
-    else if (dtype == ET_F16)
-        hipLaunchKernelGGL((detect_decode_kernel<et_f16>), grid, block, 0, s, (const et_f16*)raw, na, ny, nx, no,
-                           (long long)sb, (long long)sa, (long long)sy, (long long)sx, anchor_px, stride, z,
-                           (long long)A_total, (long long)a_offset);
-    else
-        return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }

@@ -17,8 +17,7 @@
 //   obj    : dense over every cell (b, a, y, x): BCE(logit_4, tobj) and its gradient.
 // Slot order == reference output order: offset-major [centre, left, up, right, down], then anchor,
 // then target.  Compiled with -ffp-contract=off.
-#include "et_device.h"
-#include "../../include/et_hip.h"
+#include "et_host.h"
 
 #define LOSS_NPASS 4   // 0 reliable (box+cls+tobj=iou) 1 uncertain (tobj=score) 2 uc_obj (box) 3 uc_cls (cls)
 #define LOSS_MAXL 4
@@ -847,25 +846,22 @@ extern "C" int et_scale_cast(const float* src, void* dst, int dtype, int64_t n, 
                              et_stream_t stream) {
     if (!src || !dst) return -1;
     if (n <= 0) return n == 0 ? 0 : -2;
-    const dim3 grid(et_cdiv(n, 256));
-    if (dtype == ET_F32) hipLaunchKernelGGL((scale_cast_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, src, (float*)dst, (long long)n, scale, dev_scale);
-    else if (dtype == ET_BF16 || dtype == ET_F16) {
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
         long long done = 0;
-        if (((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0 && n >= 8) {
-            const long long n8 = n / 8;
-            if (dtype == ET_BF16) hipLaunchKernelGGL((scale_cast_bf16_vec8_kernel<uint16_t>), dim3(et_cdiv(n8, 256)), dim3(256), 0, (hipStream_t)stream, src, (uint16_t*)dst, n8, scale, dev_scale);
-            else hipLaunchKernelGGL((scale_cast_bf16_vec8_kernel<et_f16>), dim3(et_cdiv(n8, 256)), dim3(256), 0, (hipStream_t)stream, src, (et_f16*)dst, n8, scale, dev_scale);
-            done = n8 * 8;
+        if constexpr (et_is_lp<T>::value) {            // scale_cast_bf16_vec8_kernel: 16-bit destinations only
+            if (((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0 && n >= 8) {
+                const long long n8 = n / 8;
+                hipLaunchKernelGGL((scale_cast_bf16_vec8_kernel<T>), dim3(et_cdiv(n8, 256)), dim3(256), 0, (hipStream_t)stream, src, (T*)dst, n8, scale, dev_scale);
+                done = n8 * 8;
+            }
         }
-        if (done < n) {
-            if (dtype == ET_BF16) hipLaunchKernelGGL((scale_cast_kernel<uint16_t>), dim3(et_cdiv(n - done, 256)), dim3(256), 0, (hipStream_t)stream, src + done,
-                                                     (uint16_t*)dst + done, (long long)(n - done), scale, dev_scale);
-            else hipLaunchKernelGGL((scale_cast_kernel<et_f16>), dim3(et_cdiv(n - done, 256)), dim3(256), 0, (hipStream_t)stream, src + done,
-                                    (et_f16*)dst + done, (long long)(n - done), scale, dev_scale);
-        }
-    } else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+        if (done < n)
+            hipLaunchKernelGGL((scale_cast_kernel<T>), dim3(et_cdiv(n - done, 256)), dim3(256), 0, (hipStream_t)stream, src + done, (T*)dst + done,
+                               (long long)(n - done), scale, dev_scale);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 // ---- domain-adaptation focal loss (DomainLoss / TargetLoss, models/loss/loss.py:376-421 with
@@ -911,23 +907,22 @@ extern "C" int et_domain_focal(const void* feat, int ldf, int dtype, int64_t P, 
                                int ldg, float* loss_sum, et_stream_t stream) {
     if (!feat || !loss_sum) return -1;
     if (P <= 0 || (label != 0 && label != 1)) return -2;
-    const dim3 grid(et_cdiv(P, 256));
-    if (dtype == ET_F32) hipLaunchKernelGGL((domain_focal_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)feat, ldf, (long long)P, label, gscale, (float*)grad, ldg, loss_sum);
-    else if (dtype == ET_BF16) hipLaunchKernelGGL((domain_focal_kernel<uint16_t>), grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)feat, ldf, (long long)P, label, gscale, (uint16_t*)grad, ldg, loss_sum);
-    else if (dtype == ET_F16) hipLaunchKernelGGL((domain_focal_kernel<et_f16>), grid, dim3(256), 0, (hipStream_t)stream, (const et_f16*)feat, ldf, (long long)P, label, gscale, (et_f16*)grad, ldg, loss_sum);
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((domain_focal_kernel<T>), dim3(et_cdiv(P, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)feat, ldf, (long long)P, label,
+                           gscale, (T*)grad, ldg, loss_sum);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_scale_inplace(void* x, int dtype, int64_t n, float alpha, const float* dev_scale, et_stream_t stream) {
     if (!x) return -1;
     if (n <= 0) return n == 0 ? 0 : -2;
-    const dim3 grid(et_cdiv(n, 256));
-    if (dtype == ET_F32) hipLaunchKernelGGL((scale_inplace_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (float*)x, (long long)n, alpha, dev_scale);
-    else if (dtype == ET_BF16) hipLaunchKernelGGL((scale_inplace_kernel<uint16_t>), grid, dim3(256), 0, (hipStream_t)stream, (uint16_t*)x, (long long)n, alpha, dev_scale);
-    else if (dtype == ET_F16) hipLaunchKernelGGL((scale_inplace_kernel<et_f16>), grid, dim3(256), 0, (hipStream_t)stream, (et_f16*)x, (long long)n, alpha, dev_scale);
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((scale_inplace_kernel<T>), dim3(et_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (T*)x, (long long)n, alpha, dev_scale);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }

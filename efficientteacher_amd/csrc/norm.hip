@@ -8,10 +8,7 @@
 // one channel vector so scale/shift live in registers.  Backward is the classic two passes:
 // reduce (sum du, sum du*xhat) -> finalize -> apply.
 #include <stdlib.h>
-#include "et_device.h"
-#include "../../include/et_hip.h"
-
-enum { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2 };
+#include "et_host.h"
 
 typedef unsigned u4raw __attribute__((ext_vector_type(4)));
 // Keeps a group of 16-byte loads where they were written: the use of all four registers in one (empty) asm statement
@@ -265,14 +262,6 @@ template <int ACT> __device__ __forceinline__ float act_grad(float u) {
     else if constexpr (ACT == ACT_RELU) return u > 0.f ? 1.f : 0.f;
     else return 1.f;
 }
-// host: instantiate `KERNEL<T, ACT>` for the run-time (dtype, act) pair
-#define ET_ACT_LAUNCH(KERNEL, T, act, ...)                                                                    \
-    do {                                                                                                      \
-        if ((act) == ACT_SILU) hipLaunchKernelGGL((KERNEL<T, ACT_SILU>), __VA_ARGS__);                        \
-        else if ((act) == ACT_RELU) hipLaunchKernelGGL((KERNEL<T, ACT_RELU>), __VA_ARGS__);                   \
-        else hipLaunchKernelGGL((KERNEL<T, ACT_NONE>), __VA_ARGS__);                                          \
-    } while (0)
-
 // The pixels one thread visits: p0 = gt / CV, p0 + pstep, ... below P (pstep = threads of the grid / CV; the grid is sized so
 // that CV divides it).  32-bit arithmetic: a 64-bit division is ~150 instructions per thread, a quarter of the work of a thread
 // that handles eight vectors.  (r04: walking the tensor from its END -- to start on the bytes the previous pass over it touched
@@ -511,10 +500,12 @@ static int ew_blocks(long long P, int CV, int vpt_default = 8) {
     return (int)blocks;
 }
 
-extern "C" int et_bn_reduce_rows(int P, int C, int dtype) {
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    return ew_blocks(P, C / vec, 16);
+// f(TypeTag<T>, std::integral_constant<int, ACT>) for the run-time (dtype, act) pair of an entry point: `KERNEL<T, ACT>` is named once
+template <typename F> static int with_dtype_act(int dtype, int act, F&& f) {
+    return with_dtype(dtype, [&](auto t) { return with_act(act, [&](auto a) { return f(t, a); }); });
 }
+
+extern "C" int et_bn_reduce_rows(int P, int C, int dtype) { return ew_blocks(P, C / et_vec(dtype), 16); }
 
 extern "C" int et_bn_finalize(const float* stats_partial, int rows, int C, double count, const float* gamma,
                               const float* beta, float eps, float momentum, float* running_mean, float* running_var,
@@ -540,22 +531,16 @@ extern "C" int et_bn_eval_affine(int C, const float* gamma, const float* beta, c
 extern "C" int et_bn_act_fwd(const void* y, int ldy, void* z, int ldz, const void* residual, int ldr, int dtype, int P,
                              int C, const float* scale, const float* shift, int act, et_stream_t stream) {
     if (!y || !z || !scale || !shift) return -1;
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    if (P <= 0 || C <= 0 || C % vec || ldy % vec || ldz % vec || (residual && ldr % vec)) return -2;
-    const int CV = C / vec;
+    const int vec = et_vec(dtype), CV = C / vec;
+    if (P <= 0 || C <= 0 || !et_whole_vecs(vec, C, ldy, ldz) || (residual && ldr % vec)) return -2;
     const dim3 grid(ew_blocks(P, CV));
-    if (dtype == ET_F32)
-        ET_ACT_LAUNCH(bn_act_fwd_kernel, float, act, grid, dim3(256), 0, (hipStream_t)stream, (const float*)y, ldy, (float*)z, ldz,
-                      (const float*)residual, ldr, P, CV, scale, shift, BnShardFwd{});
-    else if (dtype == ET_BF16)
-        ET_ACT_LAUNCH(bn_act_fwd_kernel, uint16_t, act, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)y, ldy,
-                      (uint16_t*)z, ldz, (const uint16_t*)residual, ldr, P, CV, scale, shift, BnShardFwd{});
-    else if (dtype == ET_F16)
-        ET_ACT_LAUNCH(bn_act_fwd_kernel, et_f16, act, grid, dim3(256), 0, (hipStream_t)stream, (const et_f16*)y, ldy,
-                      (et_f16*)z, ldz, (const et_f16*)residual, ldr, P, CV, scale, shift, BnShardFwd{});
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype_act(dtype, act, [&](auto t, auto a) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_act_fwd_kernel<T, decltype(a)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)y, ldy, (T*)z, ldz,
+                           (const T*)residual, ldr, P, CV, scale, shift, BnShardFwd{});
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_bn_act_bwd(const void* dz, int lddz, const void* y, int ldy, void* dy, int lddy, int dtype, int P, int C,
@@ -565,41 +550,28 @@ extern "C" int et_bn_act_bwd(const void* dz, int lddz, const void* y, int ldy, v
     // totals: 2*C fp64, zero on entry, zero again on return.  workspace (fp32 units): rows*2*C partial sums +
     // 3*C coefficients
     if (!dz || !y || !dy || !gamma || !scale || !shift || !save_mean || !save_invstd || !workspace || !totals) return -1;
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    if (P <= 0 || C <= 0 || C > 2048 || C % vec || lddz % vec || ldy % vec || lddy % vec) return -2;
-    const int CV = C / vec;
+    const int vec = et_vec(dtype), CV = C / vec;
+    if (P <= 0 || C <= 0 || C > 2048 || !et_whole_vecs(vec, C, lddz, ldy, lddy)) return -2;
     // 16 vectors per thread: the per-block partial rows and the block reduction amortise better (measured)
     const int rows = ew_blocks(P, CV, 16);
     if (ws_floats < (size_t)rows * 2 * C + 3 * (size_t)C || (((uintptr_t)totals) & 7)) return -3;
-    double* tot = totals;
     float* part = workspace;
     float* k0 = part + (size_t)rows * 2 * C;
     float* k1 = k0 + C;
     float* k2 = k1 + C;
     const dim3 grid(rows);
-    if (dtype == ET_F32)
-        ET_ACT_LAUNCH(bn_act_bwd_reduce_kernel, float, act, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dz, lddz,
-                      (const float*)y, ldy, P, CV, scale, shift, save_mean, save_invstd, part, 0);
-    else if (dtype == ET_BF16)
-        ET_ACT_LAUNCH(bn_act_bwd_reduce_kernel, uint16_t, act, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dz, lddz,
-                      (const uint16_t*)y, ldy, P, CV, scale, shift, save_mean, save_invstd, part, 0);
-    else if (dtype == ET_F16)
-        ET_ACT_LAUNCH(bn_act_bwd_reduce_kernel, et_f16, act, grid, dim3(256), 0, (hipStream_t)stream, (const et_f16*)dz, lddz,
-                      (const et_f16*)y, ldy, P, CV, scale, shift, save_mean, save_invstd, part, 0);
-    else return -2;
     const BnBwdFin fin{(float)P, gamma, save_invstd, dgamma, dbeta, k0, k1, k2, nullptr};
-    launch_rows_reduce_finalize(part, rows, C, tot, fin, (hipStream_t)stream);
-    if (dtype == ET_F32)
-        ET_ACT_LAUNCH(bn_act_bwd_apply_kernel, float, act, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dz, lddz,
-                      (const float*)y, ldy, (float*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, k0, k1, k2, BnShardBwd{});
-    else if (dtype == ET_BF16)
-        ET_ACT_LAUNCH(bn_act_bwd_apply_kernel, uint16_t, act, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dz, lddz,
-                      (const uint16_t*)y, ldy, (uint16_t*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, k0, k1, k2, BnShardBwd{});
-    else if (dtype == ET_F16)
-        ET_ACT_LAUNCH(bn_act_bwd_apply_kernel, et_f16, act, grid, dim3(256), 0, (hipStream_t)stream, (const et_f16*)dz, lddz,
-                      (const et_f16*)y, ldy, (et_f16*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, k0, k1, k2, BnShardBwd{});
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype_act(dtype, act, [&](auto t, auto a) {
+        using T = typename decltype(t)::type;
+        constexpr int ACT = decltype(a)::value;
+        hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<T, ACT>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)dz, lddz, (const T*)y, ldy,
+                           P, CV, scale, shift, save_mean, save_invstd, part, 0);
+        launch_rows_reduce_finalize(part, rows, C, totals, fin, (hipStream_t)stream);
+        hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, ACT>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)dz, lddz, (const T*)y, ldy,
+                           (T*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, k0, k1, k2, BnShardBwd{});
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_bn_act_bwd_from_partials(const void* dz, int lddz, const void* y, int ldy, void* dy, int lddy, int dtype, int P,
@@ -610,28 +582,22 @@ extern "C" int et_bn_act_bwd_from_partials(const void* dz, int lddz, const void*
     // the reduce pass has been done by the producer of dz (et_conv2d_dgrad_bn): partials (partial_rows, 2, C) hold per-tile
     // sums of du and du*y.  Finalize (one small launch) + the apply pass only.
     if (!dz || !y || !dy || !gamma || !scale || !shift || !save_mean || !save_invstd || !workspace || !totals || !partials) return -1;
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    if (P <= 0 || C <= 0 || C > 2048 || C % vec || lddz % vec || ldy % vec || lddy % vec || partial_rows <= 0) return -2;
+    const int vec = et_vec(dtype), CV = C / vec;
+    if (P <= 0 || C <= 0 || C > 2048 || !et_whole_vecs(vec, C, lddz, ldy, lddy) || partial_rows <= 0) return -2;
     if (((uintptr_t)totals) & 7) return -3;
-    const int CV = C / vec;
     float* k0 = workspace;
     float* k1 = k0 + C;
     float* k2 = k1 + C;
     const BnBwdFin fin{(float)P, gamma, save_invstd, dgamma, dbeta, k0, k1, k2, save_mean};
-    launch_rows_reduce_finalize(partials, partial_rows, C, totals, fin, (hipStream_t)stream);
     const dim3 grid(ew_blocks(P, CV, 16));
-    if (dtype == ET_F32)
-        ET_ACT_LAUNCH(bn_act_bwd_apply_kernel, float, act, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dz, lddz,
-                      (const float*)y, ldy, (float*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, k0, k1, k2, BnShardBwd{});
-    else if (dtype == ET_BF16)
-        ET_ACT_LAUNCH(bn_act_bwd_apply_kernel, uint16_t, act, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dz, lddz,
-                      (const uint16_t*)y, ldy, (uint16_t*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, k0, k1, k2, BnShardBwd{});
-    else if (dtype == ET_F16)
-        ET_ACT_LAUNCH(bn_act_bwd_apply_kernel, et_f16, act, grid, dim3(256), 0, (hipStream_t)stream, (const et_f16*)dz, lddz,
-                      (const et_f16*)y, ldy, (et_f16*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, k0, k1, k2, BnShardBwd{});
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype_act(dtype, act, [&](auto t, auto a) {
+        using T = typename decltype(t)::type;
+        launch_rows_reduce_finalize(partials, partial_rows, C, totals, fin, (hipStream_t)stream);
+        hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, decltype(a)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)dz, lddz,
+                           (const T*)y, ldy, (T*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, k0, k1, k2, BnShardBwd{});
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_bn_act_fwd_sharded(const void* y, int ldy, void* z, int ldz, const void* residual, int ldr, int dtype, int P, int C,
@@ -639,24 +605,18 @@ extern "C" int et_bn_act_fwd_sharded(const void* y, int ldy, void* z, int ldz, c
                                      float momentum, float* running_mean, float* running_var, float* scale, float* shift,
                                      float* save_mean, float* save_invstd, int act, et_stream_t stream) {
     if (!y || !z || !shards || !gamma || !beta || !scale || !shift) return -1;
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    if (P <= 0 || C <= 0 || C > BN_SHARD_MAX_C || C % vec || ldy % vec || ldz % vec || (residual && ldr % vec) || shard_ld < C || count <= 0) return -2;
+    const int vec = et_vec(dtype), CV = C / vec;
+    if (P <= 0 || C <= 0 || C > BN_SHARD_MAX_C || !et_whole_vecs(vec, C, ldy, ldz) || (residual && ldr % vec) || shard_ld < C || count <= 0) return -2;
     if ((running_mean == nullptr) != (running_var == nullptr) || (save_mean == nullptr) != (save_invstd == nullptr)) return -2;
-    const int CV = C / vec;
     const dim3 grid(ew_blocks(P, CV));
     const BnShardFwd q{shards, shard_ld, BnFwdFin{count, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, save_mean, save_invstd}};
-    if (dtype == ET_F32)
-        ET_ACT_LAUNCH(bn_act_fwd_kernel, float, act, grid, dim3(256), 0, (hipStream_t)stream, (const float*)y, ldy, (float*)z, ldz,
-                      (const float*)residual, ldr, P, CV, nullptr, nullptr, q);
-    else if (dtype == ET_BF16)
-        ET_ACT_LAUNCH(bn_act_fwd_kernel, uint16_t, act, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)y, ldy,
-                      (uint16_t*)z, ldz, (const uint16_t*)residual, ldr, P, CV, nullptr, nullptr, q);
-    else if (dtype == ET_F16)
-        ET_ACT_LAUNCH(bn_act_fwd_kernel, et_f16, act, grid, dim3(256), 0, (hipStream_t)stream, (const et_f16*)y, ldy,
-                      (et_f16*)z, ldz, (const et_f16*)residual, ldr, P, CV, nullptr, nullptr, q);
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype_act(dtype, act, [&](auto t, auto a) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_act_fwd_kernel<T, decltype(a)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)y, ldy, (T*)z, ldz,
+                           (const T*)residual, ldr, P, CV, nullptr, nullptr, q);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_bn_act_bwd_sharded(const void* dz, int lddz, const void* y, int ldy, void* dy, int lddy, int dtype, int P, int C,
@@ -664,55 +624,35 @@ extern "C" int et_bn_act_bwd_sharded(const void* dz, int lddz, const void* y, in
                                      const float* save_invstd, int act, float* dgamma, float* dbeta, float* shards, int shard_ld,
                                      int reduce, et_stream_t stream) {
     if (!dz || !y || !dy || !gamma || !scale || !shift || !save_mean || !save_invstd || !shards) return -1;
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    if (P <= 0 || C <= 0 || C > BN_SHARD_MAX_C || C % vec || lddz % vec || ldy % vec || lddy % vec || shard_ld < C) return -2;
-    const int CV = C / vec;
+    const int vec = et_vec(dtype), CV = C / vec;
+    if (P <= 0 || C <= 0 || C > BN_SHARD_MAX_C || !et_whole_vecs(vec, C, lddz, ldy, lddy) || shard_ld < C) return -2;
     const dim3 grid(ew_blocks(P, CV, 16));
-    if (reduce) {
-        if (dtype == ET_F32)
-            ET_ACT_LAUNCH(bn_act_bwd_reduce_kernel, float, act, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dz, lddz,
-                          (const float*)y, ldy, P, CV, scale, shift, save_mean, save_invstd, shards, shard_ld);
-        else if (dtype == ET_BF16)
-            ET_ACT_LAUNCH(bn_act_bwd_reduce_kernel, uint16_t, act, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dz, lddz,
-                          (const uint16_t*)y, ldy, P, CV, scale, shift, save_mean, save_invstd, shards, shard_ld);
-        else if (dtype == ET_F16)
-            ET_ACT_LAUNCH(bn_act_bwd_reduce_kernel, et_f16, act, grid, dim3(256), 0, (hipStream_t)stream, (const et_f16*)dz, lddz,
-                          (const et_f16*)y, ldy, P, CV, scale, shift, save_mean, save_invstd, shards, shard_ld);
-        else return -2;
-    }
     // the reduce pass leaves sums of du * xhat; a conv epilogue leaves sums of du * y (converted with the saved mean / invstd)
     const BnShardBwd q{shards, shard_ld, BnBwdFin{(float)P, gamma, save_invstd, dgamma, dbeta, nullptr, nullptr, nullptr, reduce ? nullptr : save_mean}};
-    if (dtype == ET_F32)
-        ET_ACT_LAUNCH(bn_act_bwd_apply_kernel, float, act, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dz, lddz,
-                      (const float*)y, ldy, (float*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, nullptr, nullptr, nullptr, q);
-    else if (dtype == ET_BF16)
-        ET_ACT_LAUNCH(bn_act_bwd_apply_kernel, uint16_t, act, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dz, lddz,
-                      (const uint16_t*)y, ldy, (uint16_t*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, nullptr, nullptr, nullptr, q);
-    else if (dtype == ET_F16)
-        ET_ACT_LAUNCH(bn_act_bwd_apply_kernel, et_f16, act, grid, dim3(256), 0, (hipStream_t)stream, (const et_f16*)dz, lddz,
-                      (const et_f16*)y, ldy, (et_f16*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, nullptr, nullptr, nullptr, q);
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype_act(dtype, act, [&](auto t, auto a) {
+        using T = typename decltype(t)::type;
+        constexpr int ACT = decltype(a)::value;
+        if (reduce)
+            hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<T, ACT>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)dz, lddz, (const T*)y,
+                               ldy, P, CV, scale, shift, save_mean, save_invstd, shards, shard_ld);
+        hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, ACT>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)dz, lddz, (const T*)y, ldy,
+                           (T*)dy, lddy, P, CV, scale, shift, save_mean, save_invstd, nullptr, nullptr, nullptr, q);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_act_bwd(const void* dz, int lddz, const void* y, int ldy, void* dy, int lddy, int dtype, int P, int C,
                           int act, et_stream_t stream) {
     if (!dz || !y || !dy) return -1;
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    if (P <= 0 || C <= 0 || C % vec || lddz % vec || ldy % vec || lddy % vec) return -2;
-    const int CV = C / vec;
+    const int vec = et_vec(dtype), CV = C / vec;
+    if (P <= 0 || C <= 0 || !et_whole_vecs(vec, C, lddz, ldy, lddy)) return -2;
     const dim3 grid(ew_blocks(P, CV));
-    if (dtype == ET_F32)
-        ET_ACT_LAUNCH(act_bwd_kernel, float, act, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dz, lddz, (const float*)y, ldy,
-                      (float*)dy, lddy, P, CV);
-    else if (dtype == ET_BF16)
-        ET_ACT_LAUNCH(act_bwd_kernel, uint16_t, act, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dz, lddz,
-                      (const uint16_t*)y, ldy, (uint16_t*)dy, lddy, P, CV);
-    else if (dtype == ET_F16)
-        ET_ACT_LAUNCH(act_bwd_kernel, et_f16, act, grid, dim3(256), 0, (hipStream_t)stream, (const et_f16*)dz, lddz,
-                      (const et_f16*)y, ldy, (et_f16*)dy, lddy, P, CV);
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype_act(dtype, act, [&](auto t, auto a) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((act_bwd_kernel<T, decltype(a)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)dz, lddz, (const T*)y,
+                           ldy, (T*)dy, lddy, P, CV);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }

@@ -7,9 +7,8 @@
 //          GradScaler-style 1/scale (trainer/trainer.py:399-400) and an optional bf16 shadow copy of
 //          the updated weights for the MFMA kernels, all in the same pass.
 // Compiled with -ffp-contract=off.
-#include "et_device.h"
+#include "et_host.h"
 #include <math.h>
-#include "../../include/et_hip.h"
 
 // 16-bit shadow copy of an updated weight in the compute format (ET_BF16 / ET_F16)
 __device__ __forceinline__ uint16_t lp_of(float v, int shadow_dtype) { return shadow_dtype == ET_F16 ? et_f2h(v) : et_f2bf(v); }
@@ -231,18 +230,22 @@ extern "C" int et_cast_f32_to_lp(const float* src, void* dst, int dtype, int64_t
     if (!src || !dst) return -1;
     if (dtype != ET_BF16 && dtype != ET_F16) return -2;
     if (n <= 0) return n == 0 ? 0 : -2;
-    long long done = 0;
-    if (((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0 && n >= 8) {
-        const long long n8 = n / 8;
-        if (dtype == ET_BF16) hipLaunchKernelGGL((cast_bf16_vec8_kernel<uint16_t>), dim3(et_cdiv(n8, 256)), dim3(256), 0, (hipStream_t)stream, src, (uint16_t*)dst, n8);
-        else hipLaunchKernelGGL((cast_bf16_vec8_kernel<et_f16>), dim3(et_cdiv(n8, 256)), dim3(256), 0, (hipStream_t)stream, src, (et_f16*)dst, n8);
-        done = n8 * 8;
-    }
-    if (done < n)
-        hipLaunchKernelGGL(cast_bf16_kernel, dim3(et_cdiv(n - done, 256)), dim3(256), 0, (hipStream_t)stream, src + done,
-                           (uint16_t*)dst + done, (long long)(n - done), dtype);
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        long long done = 0;
+        if constexpr (et_is_lp<T>::value) {            // cast_bf16_vec8_kernel: 16-bit destinations only (ET_F32 was refused above)
+            if (((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0 && n >= 8) {
+                const long long n8 = n / 8;
+                hipLaunchKernelGGL((cast_bf16_vec8_kernel<T>), dim3(et_cdiv(n8, 256)), dim3(256), 0, (hipStream_t)stream, src, (T*)dst, n8);
+                done = n8 * 8;
+            }
+        }
+        if (done < n)
+            hipLaunchKernelGGL(cast_bf16_kernel, dim3(et_cdiv(n - done, 256)), dim3(256), 0, (hipStream_t)stream, src + done,
+                               (uint16_t*)dst + done, (long long)(n - done), dtype);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 // ---- loss scaler (fp16 mode) ------------------------------------------------------------------------------------

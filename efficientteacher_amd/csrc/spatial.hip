@@ -6,8 +6,7 @@
 //     concat buffer;
 //   * nearest 2x upsample (models/neck/yolov5_neck.py:60,64) written straight into the channel slice
 //     of the following concat buffer, and its backward (sum of the 4 children).
-#include "et_device.h"
-#include "../../include/et_hip.h"
+#include "et_host.h"
 
 template <typename T>
 __global__ __launch_bounds__(256) void pack_input_kernel(const float* __restrict__ x, T* __restrict__ y, int C, int HW, long long total) {
@@ -222,23 +221,19 @@ extern "C" int et_pack_input(const float* x_nchw, void* y_nhwc8, int dtype, int 
     if (B <= 0 || C <= 0 || C > 8 || H <= 0 || W <= 0) return -2;
     const long long total = (long long)B * H * W;
     if (total >= (1ll << 31)) return -2;               // the kernels index with 32-bit arithmetic
-    const dim3 grid(et_cdiv(total, 256));
-    if (dtype == ET_F32) hipLaunchKernelGGL((pack_input_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, x_nchw, (float*)y_nhwc8, C, H * W, total);
-    else if (dtype == ET_BF16) {
-        if (C <= 4 && (H * W) % 4 == 0 && ((((uintptr_t)x_nchw) | ((uintptr_t)y_nhwc8)) & 15) == 0)
-            hipLaunchKernelGGL((pack_input4_bf16_kernel<float>), dim3(et_cdiv(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, x_nchw,
-                               (uint16_t*)y_nhwc8, C, H * W / 4, total / 4, 1.0f);
-        else
-            hipLaunchKernelGGL((pack_input_kernel<uint16_t>), grid, dim3(256), 0, (hipStream_t)stream, x_nchw, (uint16_t*)y_nhwc8, C, H * W, total);
-    } else if (dtype == ET_F16) {
-        if (C <= 4 && (H * W) % 4 == 0 && ((((uintptr_t)x_nchw) | ((uintptr_t)y_nhwc8)) & 15) == 0)
-            hipLaunchKernelGGL((pack_input4_bf16_kernel<float, et_f16>), dim3(et_cdiv(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, x_nchw,
-                               (et_f16*)y_nhwc8, C, H * W / 4, total / 4, 1.0f);
-        else
-            hipLaunchKernelGGL((pack_input_kernel<et_f16>), grid, dim3(256), 0, (hipStream_t)stream, x_nchw, (et_f16*)y_nhwc8, C, H * W, total);
-    } else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        const bool quads = et_is_lp<T>::value && C <= 4 && (H * W) % 4 == 0 && ((((uintptr_t)x_nchw) | ((uintptr_t)y_nhwc8)) & 15) == 0;
+        if constexpr (et_is_lp<T>::value) {            // pack_input4_bf16_kernel: 16-bit outputs only
+            if (quads)
+                hipLaunchKernelGGL((pack_input4_bf16_kernel<float, T>), dim3(et_cdiv(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, x_nchw,
+                                   (T*)y_nhwc8, C, H * W / 4, total / 4, 1.0f);
+        }
+        if (!quads)
+            hipLaunchKernelGGL((pack_input_kernel<T>), dim3(et_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x_nchw, (T*)y_nhwc8, C, H * W, total);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_pack_input_u8(const uint8_t* x_nchw, void* y_nhwc8, int dtype, int B, int C, int H, int W, float norm_scale,
@@ -247,84 +242,81 @@ extern "C" int et_pack_input_u8(const uint8_t* x_nchw, void* y_nhwc8, int dtype,
     if (B <= 0 || C <= 0 || C > 8 || H <= 0 || W <= 0 || !(norm_scale > 0.f)) return -2;
     const long long total = (long long)B * H * W;
     if (total >= (1ll << 31)) return -2;               // the kernels index with 32-bit arithmetic
-    const dim3 grid(et_cdiv(total, 256));
-    if (dtype == ET_F32) hipLaunchKernelGGL((pack_input_u8_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, x_nchw, (float*)y_nhwc8, C, H * W, total, norm_scale);
-    else if (dtype == ET_BF16) {
-        if (C <= 4 && (H * W) % 4 == 0 && (((uintptr_t)x_nchw) & 3) == 0 && (((uintptr_t)y_nhwc8) & 15) == 0)
-            hipLaunchKernelGGL((pack_input4_bf16_kernel<uint8_t>), dim3(et_cdiv(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, x_nchw,
-                               (uint16_t*)y_nhwc8, C, H * W / 4, total / 4, norm_scale);
-        else
-            hipLaunchKernelGGL((pack_input_u8_kernel<uint16_t>), grid, dim3(256), 0, (hipStream_t)stream, x_nchw, (uint16_t*)y_nhwc8, C, H * W, total, norm_scale);
-    } else if (dtype == ET_F16) {
-        if (C <= 4 && (H * W) % 4 == 0 && (((uintptr_t)x_nchw) & 3) == 0 && (((uintptr_t)y_nhwc8) & 15) == 0)
-            hipLaunchKernelGGL((pack_input4_bf16_kernel<uint8_t, et_f16>), dim3(et_cdiv(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, x_nchw,
-                               (et_f16*)y_nhwc8, C, H * W / 4, total / 4, norm_scale);
-        else
-            hipLaunchKernelGGL((pack_input_u8_kernel<et_f16>), grid, dim3(256), 0, (hipStream_t)stream, x_nchw, (et_f16*)y_nhwc8, C, H * W, total, norm_scale);
-    } else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        const bool quads = et_is_lp<T>::value && C <= 4 && (H * W) % 4 == 0 && (((uintptr_t)x_nchw) & 3) == 0 && (((uintptr_t)y_nhwc8) & 15) == 0;
+        if constexpr (et_is_lp<T>::value) {            // pack_input4_bf16_kernel: 16-bit outputs only
+            if (quads)
+                hipLaunchKernelGGL((pack_input4_bf16_kernel<uint8_t, T>), dim3(et_cdiv(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, x_nchw,
+                                   (T*)y_nhwc8, C, H * W / 4, total / 4, norm_scale);
+        }
+        if (!quads)
+            hipLaunchKernelGGL((pack_input_u8_kernel<T>), dim3(et_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x_nchw, (T*)y_nhwc8, C, H * W, total,
+                               norm_scale);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_maxpool5_fwd(const void* x, int ldx, void* y, int ldy, uint8_t* argmax, int dtype, int B, int H, int W, int C,
                                et_stream_t stream) {
     if (!x || !y || !argmax) return -1;
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    if (B <= 0 || C % vec || ldx % vec || ldy % vec) return -2;
-    const int CV = C / vec;
+    const int vec = et_vec(dtype), CV = C / vec;
+    if (B <= 0 || !et_whole_vecs(vec, C, ldx, ldy)) return -2;
     const long long total = (long long)B * H * W * CV;
     if (total >= (1ll << 31)) return -2;               // the kernels index with 32-bit arithmetic
-    if (dtype == ET_F32) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((maxpool5_fwd_kernel<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)x, ldx, (float*)y, ldy, argmax, H, W, CV, total); }
-    else if (dtype == ET_BF16) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((maxpool5_fwd_kernel<uint16_t>), g, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, ldx, (uint16_t*)y, ldy, argmax, H, W, CV, total); }
-    else if (dtype == ET_F16) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((maxpool5_fwd_kernel<et_f16>), g, dim3(256), 0, (hipStream_t)stream, (const et_f16*)x, ldx, (et_f16*)y, ldy, argmax, H, W, CV, total); }
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((maxpool5_fwd_kernel<T>), dim3(et_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, (T*)y, ldy, argmax,
+                           H, W, CV, total);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_maxpool5_bwd(const void* dy, int lddy, const uint8_t* argmax, const void* base, int ldb, void* dx, int lddx,
                                int dtype, int B, int H, int W, int C, et_stream_t stream) {
     if (!dy || !dx || !argmax) return -1;
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    if (B <= 0 || C % vec || lddy % vec || lddx % vec || (base && ldb % vec)) return -2;
-    const int CV = C / vec;
+    const int vec = et_vec(dtype), CV = C / vec;
+    if (B <= 0 || !et_whole_vecs(vec, C, lddy, lddx) || (base && ldb % vec)) return -2;
     const long long total = (long long)B * H * W * CV;
     if (total >= (1ll << 31)) return -2;               // the kernels index with 32-bit arithmetic
-    if (dtype == ET_F32) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((maxpool5_bwd_kernel<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)dy, lddy, argmax, (const float*)base, ldb, (float*)dx, lddx, H, W, CV, total); }
-    else if (dtype == ET_BF16) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((maxpool5_bwd_kernel<uint16_t>), g, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dy, lddy, argmax, (const uint16_t*)base, ldb, (uint16_t*)dx, lddx, H, W, CV, total); }
-    else if (dtype == ET_F16) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((maxpool5_bwd_kernel<et_f16>), g, dim3(256), 0, (hipStream_t)stream, (const et_f16*)dy, lddy, argmax, (const et_f16*)base, ldb, (et_f16*)dx, lddx, H, W, CV, total); }
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((maxpool5_bwd_kernel<T>), dim3(et_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, lddy, argmax,
+                           (const T*)base, ldb, (T*)dx, lddx, H, W, CV, total);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_upsample2x_fwd(const void* x, int ldx, void* y, int ldy, int dtype, int B, int H, int W, int C, et_stream_t stream) {
     if (!x || !y) return -1;
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    if (B <= 0 || C % vec || ldx % vec || ldy % vec) return -2;
-    const int CV = C / vec;
+    const int vec = et_vec(dtype), CV = C / vec;
+    if (B <= 0 || !et_whole_vecs(vec, C, ldx, ldy)) return -2;
     const long long total = (long long)B * 4 * H * W * CV;
     if (total >= (1ll << 31)) return -2;               // the kernels index with 32-bit arithmetic
-    if (dtype == ET_F32) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((upsample2x_fwd_kernel<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)x, ldx, (float*)y, ldy, H, W, CV, total); }
-    else if (dtype == ET_BF16) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((upsample2x_fwd_kernel<uint16_t>), g, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, ldx, (uint16_t*)y, ldy, H, W, CV, total); }
-    else if (dtype == ET_F16) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((upsample2x_fwd_kernel<et_f16>), g, dim3(256), 0, (hipStream_t)stream, (const et_f16*)x, ldx, (et_f16*)y, ldy, H, W, CV, total); }
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((upsample2x_fwd_kernel<T>), dim3(et_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, (T*)y, ldy, H, W,
+                           CV, total);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int et_upsample2x_bwd(const void* dy, int lddy, void* dx, int lddx, int dtype, int B, int H, int W, int C, int accumulate,
                                  et_stream_t stream) {
     if (!dy || !dx) return -1;
-    const int vec = dtype == ET_F32 ? 4 : 8;
-    if (B <= 0 || C % vec || lddy % vec || lddx % vec) return -2;
-    const int CV = C / vec;
+    const int vec = et_vec(dtype), CV = C / vec;
+    if (B <= 0 || !et_whole_vecs(vec, C, lddy, lddx)) return -2;
     const long long total = (long long)B * H * W * CV;
     if (total >= (1ll << 31)) return -2;               // the kernels index with 32-bit arithmetic
-    if (dtype == ET_F32) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((upsample2x_bwd_kernel<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)dy, lddy, (float*)dx, lddx, H, W, CV, total, accumulate); }
-    else if (dtype == ET_BF16) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((upsample2x_bwd_kernel<uint16_t>), g, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dy, lddy, (uint16_t*)dx, lddx, H, W, CV, total, accumulate); }
-    else if (dtype == ET_F16) { const dim3 g(et_cdiv(total, 256)); hipLaunchKernelGGL((upsample2x_bwd_kernel<et_f16>), g, dim3(256), 0, (hipStream_t)stream, (const et_f16*)dy, lddy, (et_f16*)dx, lddx, H, W, CV, total, accumulate); }
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((upsample2x_bwd_kernel<T>), dim3(et_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, lddy, (T*)dx, lddx,
+                           H, W, CV, total, accumulate);
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }

@@ -16,8 +16,7 @@
 //                  metrics only occur at exactly 0 (anchor inside the gt whose predicted box misses it), where the pick has
 //                  no effect on the loss (its target score is 0); tests compare on the anchors with a non-zero target.
 // Compiled with -ffp-contract=off (index decisions depend on fp32 results).
-#include "et_device.h"
-#include "../../include/et_hip.h"
+#include "et_host.h"
 #include <math.h>
 
 template <typename T>
@@ -61,21 +60,13 @@ extern "C" int et_v8_decode(const void* reg, int ld_reg, const void* cls, int ld
     if (!reg || !cls || !out) return -1;
     if (B <= 0 || H <= 0 || W <= 0 || reg_max < 0 || reg_max > 31 || nc <= 0) return -2;
     const long long total = (long long)B * H * W;
-    const dim3 grid(et_cdiv(total, 256));
-    if (dtype == ET_F32)
-        hipLaunchKernelGGL((v8_decode_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)reg, ld_reg, (const float*)cls,
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((v8_decode_kernel<T>), dim3(et_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)reg, ld_reg, (const T*)cls,
                            ld_cls, B, H, W, reg_max, nc, stride, cell_offset, out, (long long)A_total, (long long)a_offset);
-    else if (dtype == ET_BF16)
-        hipLaunchKernelGGL((v8_decode_kernel<uint16_t>), grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)reg, ld_reg,
-                           (const uint16_t*)cls, ld_cls, B, H, W, reg_max, nc, stride, cell_offset, out, (long long)A_total,
-                           (long long)a_offset);
-    else if (dtype == ET_F16)
-        hipLaunchKernelGGL((v8_decode_kernel<et_f16>), grid, dim3(256), 0, (hipStream_t)stream, (const et_f16*)reg, ld_reg,
-                           (const et_f16*)cls, ld_cls, B, H, W, reg_max, nc, stride, cell_offset, out, (long long)A_total,
-                           (long long)a_offset);
-    else return -2;
-    ET_CHECK_LAUNCH();
-    return 0;
+        ET_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 // ---- TaskAlignedAssigner ----------------------------------------------------------------------------------------

@@ -10,7 +10,9 @@ CSRC = os.path.join(ROOT, "efficientteacher_amd", "csrc")
 OUT = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT, "libet_emu.so")
 CXX = os.environ.get("ET_EMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-EXACT = {"nms.hip", "loss.hip", "pseudo_label.hip", "detect.hip", "optim.hip", "tal.hip", "augment.hip"}
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from efficientteacher_amd.csrc.build import EXACT  # noqa: E402  (the files built with -ffp-contract=off: ONE list, the product's)
 FLAGS = ["-x", "c++", "-std=c++17", "-O2", "-fPIC", "-g0", "-Wno-unused-function", "-Wno-unknown-attributes",
          "-Wno-unused-value", "-fno-strict-aliasing",
          "-I", os.path.join(HERE, "include"), "-I", os.path.join(ROOT, "include")]
