@@ -613,20 +613,26 @@ class GradReverseFn(Function):  # reference models/detector/yolo_ssod.py:158-171
 
 class DomainFocalFn(Function):
     """0.5 * mean over the pixels of all levels of -(1-p)^2 log p  (DomainLoss label 0 / TargetLoss
-    label 1, models/loss/loss.py:376-421).  Inputs: the netD logits as (B,H,W,2) NHWC tensors."""
+    label 1, models/loss/loss.py:376-421).  Inputs: the netD logits as (B,H,W,2) NHWC tensors.
+    The saved gradient is fp32 whatever the logits' dtype and is rounded to it ONCE, in backward, with the upstream factor folded
+    in (as YoloLossFn does): stored in the logits' dtype it carried only 0.5/total -- ~3e-5 on a 640-pixel pyramid, in or below
+    fp16's subnormal range before the loss scale could lift it -- and was rounded a second time by the upstream scaling."""
 
     @staticmethod
     def forward(ctx, label, *feats):
         total = sum(f.shape[0] * f.shape[1] * f.shape[2] for f in feats)
         acc = torch.zeros(1, dtype=torch.float32, device=feats[0].device)
-        grads = [ops.domain_focal(f, label, 0.5 / total, acc, want_grad=True) for f in feats]
+        # et_domain_focal writes the gradient in the dtype it reads: the kernel's arithmetic is fp32 either way, the fp32 copy of
+        # the 16-bit logits is exact
+        grads = [ops.domain_focal(f if f.dtype == torch.float32 else f.float(), label, 0.5 / total, acc, want_grad=True) for f in feats]
+        ctx.dtypes = [f.dtype for f in feats]
         ctx.save_for_backward(*grads)
         return ops.scale_cast(acc, torch.float32, scale=0.5 / total)
 
     @staticmethod
     def backward(ctx, gout):
         g = gout.reshape(1).float().contiguous()
-        return (None, *[ops.scale_inplace(gr.clone(), 1.0, dev_scale=g) for gr in ctx.saved_tensors])
+        return (None, *[ops.scale_cast(gr, dt, scale=1.0, dev_scale=g) for gr, dt in zip(ctx.saved_tensors, ctx.dtypes)])
 
 
 def _dense_or_slice(g):

@@ -900,7 +900,15 @@ __global__ __launch_bounds__(256) void scale_inplace_kernel(T* __restrict__ x, l
                                                             const float* __restrict__ dev_scale) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const float f = dev_scale ? alpha * dev_scale[0] : alpha;
-    if (i < n) x[i] = et_elem<T>::st(et_elem<T>::ld(x[i]) * f);
+    if (i < n) {
+        // the product stays an fp32 value of its own: fused into the fp16 store (v_fma_mixlo_f16 x, f, +0) a zero loses its sign, and
+        // GradReverse's -1 is the exact negation of every element (tests/test_lp_logits.py::test_grad_reverse_is_exact_negation)
+        float v = et_elem<T>::ld(x[i]) * f;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(v));
+#endif
+        x[i] = et_elem<T>::st(v);
+    }
 }
 
 extern "C" int et_domain_focal(const void* feat, int ldf, int dtype, int64_t P, int label, float gscale, void* grad,

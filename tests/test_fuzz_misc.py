@@ -154,9 +154,13 @@ def test_spatial_ops_random_sizes(dev, seed):
         dy = torch.randn((N, H, W, C), generator=g).to(dt)
         pr.backward(dy.float().permute(0, 3, 1, 2))
         dx = ops.maxpool5_bwd(dev.t(dy), idx)
-        # ties inside a window: torch routes the gradient to ONE of the equal maxima; compare where the input has no tie
-        assert (dx.float().cpu() - xr.grad.permute(0, 2, 3, 1)).abs().max().item() <= (2e-2 if dt == torch.bfloat16 else 1e-5) * max(1.0, xr.grad.abs().max().item()) \
-            or dt == torch.bfloat16
+        # ties inside a window (frequent among bf16 values): torch routes the gradient to the FIRST of the equal maxima in scan
+        # order and so does the kernel (test_norm_spatial.py::test_sppf_pool_chain pins that on plateaus), so every element is
+        # compared.  The kernel sums in fp32 and rounds once: per element u |ref| (u = 2^-8 bf16, 0 fp32) + 1e-5 max|ref| for the
+        # summation order of up to 25 fp32 terms
+        gref = xr.grad.permute(0, 2, 3, 1)
+        bound = (2.0 ** -8 if dt == torch.bfloat16 else 0.0) * gref.abs() + 1e-5 * gref.abs().max()
+        assert ((dx.float().cpu() - gref).abs() <= bound).all(), (N, H, W, C, dt)
         up = ops.upsample2x_fwd(dev.t(x))
         assert torch.equal(up.cpu(), x.repeat_interleave(2, 1).repeat_interleave(2, 2))
         du = torch.randn((N, 2 * H, 2 * W, C), generator=g).to(dt)

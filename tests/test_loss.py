@@ -72,8 +72,8 @@ def test_student_match_loss_golden(hip, tag):
 
 @pytest.mark.parametrize("seed", [0, 1])
 def test_loss_vs_oracle_with_duplicates_and_views(hip, seed):
-    """Many targets on a small grid (duplicate cells: last-writer-wins rule), logits as strided
-    head views over a (B, ny, nx, 256) buffer, bf16 logits."""
+    """Many targets on a small grid (duplicate cells: last-writer-wins rule), fp32 logits as strided
+    head views over a (B, ny, nx, 256) buffer.  The same inputs as bf16 / fp16 head views: tests/test_lp_logits.py."""
     from efficientteacher_amd.autograd import head_view
     from efficientteacher_amd.models.loss import ComputeLoss
     rng = np.random.default_rng(seed)

@@ -133,14 +133,19 @@ def test_vs_oracle(hip, seed, B, n_per, dtype):
     lo, io = o_loss.ota_loss(po, torch.from_numpy(t), torch.from_numpy(g["anchors"]), closs._strides, nc=nc, box_w=closs.box_w,
                              obj_w=closs.obj_w, cls_w=closs.cls_w, anchor_t=closs.anchor_t)
     lo.backward()
-    tol = 1e-4 if dtype == torch.float32 else 2e-2
-    assert abs(loss.item() - lo.item()) <= tol * abs(lo.item()), (loss.item(), lo.item())
+    # the bf16 logits are pre-rounded and the kernel's arithmetic is fp32 in every mode: the values meet the fp32 bound, and the
+    # gradient is rounded once to bf16 (unit roundoff 2^-8), per element, on top of the fp32 kernel-vs-oracle term
+    # (tests/test_lp_logits.py::test_simota_head_views holds the same inputs to these bounds on strided head views, fp16 included)
+    assert abs(loss.item() - lo.item()) <= 1e-4 * abs(lo.item()), (loss.item(), lo.item())
     for k in ("box", "obj", "cls"):
-        assert abs(items[k].item() - io[k].item()) <= tol * abs(io[k].item()) + 1e-6, k
+        assert abs(items[k].item() - io[k].item()) <= 1e-4 * abs(io[k].item()) + 1e-6, k
     for a, b in zip(p, po):
         ref = b.grad.numpy()
-        err = np.abs(a.grad.float().cpu().numpy() - ref).max()
-        assert err <= tol * np.abs(ref).max() + 1e-7, err
+        err = np.abs(a.grad.float().cpu().numpy() - ref)
+        if dtype == torch.float32:
+            assert err.max() <= 1e-4 * np.abs(ref).max() + 1e-7, err.max()
+        else:
+            assert (err <= 2.0 ** -8 * np.abs(ref) + 2e-4 * np.abs(ref).max()).all(), (err.max(), np.abs(ref).max())
 
 
 def test_padding_rows_and_empty(hip):
