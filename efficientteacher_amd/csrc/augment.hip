@@ -33,6 +33,50 @@ struct AugArgs {
 
 __device__ __forceinline__ int aug_round(double v) { return (int)rint(v); }       // cvRound: half to even (default rounding mode)
 
+// ---- cv2.warpAffine, INTER_LINEAR, BORDER_CONSTANT: AB_BITS 10, INTER_BITS 5, weights * 2^15.  M: the dst -> src map; (x, y): the
+// destination pixel.  -> the top-left tap (sx, sy) and the weights of the taps (sy, sx), (sy, sx + 1), (sy + 1, sx), (sy + 1, sx + 1);
+// the pixel is (sum w * tap + (1 << 14)) >> 15.  Shared by strong_view_kernel and labeled_mosaic_kernel.
+__device__ __forceinline__ void aug_warp_taps(const double* M, int x, int y, int& sx, int& sy, int w[4]) {
+    const int round_delta = 16;                                           // AB_SCALE / INTER_TAB_SIZE / 2
+    const int X0 = aug_round((M[1] * y + M[2]) * 1024.0) + round_delta, Y0 = aug_round((M[4] * y + M[5]) * 1024.0) + round_delta;
+    const int X = (X0 + aug_round(M[0] * x * 1024.0)) >> 5, Y = (Y0 + aug_round(M[3] * x * 1024.0)) >> 5;
+    sx = X >> 5; sy = Y >> 5;
+    const int fx = X & 31, fy = Y & 31;
+    w[0] = (32 - fx) * (32 - fy) * 32; w[1] = fx * (32 - fy) * 32; w[2] = (32 - fx) * fy * 32; w[3] = fx * fy * 32;
+}
+
+// ---- augment_hsv on one pixel: cvtColor RGB -> HSV, the three LUTs L[3][256] (hue, sat, val), cvtColor HSV -> RGB
+__device__ __forceinline__ void aug_hsv_lut(const unsigned char* L, int& r, int& g, int& bl) {
+    // ---- cvtColor RGB -> HSV (8 bit, H in [0,180)): integer division tables with hsv_shift = 12
+    const int v = max(max(r, g), bl), vmin = min(min(r, g), bl);
+    const int diff = v - vmin;
+    const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
+    const int sdiv = v ? aug_round((255 << 12) / (double)v) : 0;
+    const int hdiv = diff ? aug_round((180 << 12) / (6.0 * diff)) : 0;
+    const int s = (diff * sdiv + (1 << 11)) >> 12;
+    int h = (vr & (g - bl)) + (~vr & ((vg & (bl - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
+    h = (h * hdiv + (1 << 11)) >> 12;
+    h += h < 0 ? 180 : 0;
+    const int h2 = L[h & 255], s2 = L[256 + s], v2 = L[512 + v];
+    // ---- cvtColor HSV -> RGB (8 bit): float sector arithmetic, cvRound to uchar
+    const float fs = s2 * (1.f / 255.f), fv = v2 * (1.f / 255.f);
+    float fr, fg, fb;
+    if (s2 == 0) {
+        fr = fg = fb = fv;
+    } else {
+        float hh = h2 * (6.f / 180.f);
+        int sector = (int)floorf(hh);
+        hh -= sector;
+        if ((unsigned)sector >= 6u) { sector = 0; hh = 0.f; }
+        const float tab[4] = {fv, fv * (1.f - fs), fv * (1.f - fs * hh), fv * (1.f - fs * (1.f - hh))};
+        const int sd[6][3] = {{1, 3, 0}, {1, 0, 2}, {3, 0, 1}, {0, 2, 1}, {0, 1, 3}, {2, 1, 0}};      // b, g, r
+        fb = tab[sd[sector][0]]; fg = tab[sd[sector][1]]; fr = tab[sd[sector][2]];
+    }
+    r = min(max(aug_round(fr * 255.f), 0), 255);
+    g = min(max(aug_round(fg * 255.f), 0), 255);
+    bl = min(max(aug_round(fb * 255.f), 0), 255);
+}
+
 __global__ __launch_bounds__(256) void strong_view_kernel(AugArgs a) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long plane = (long long)a.H * a.W;
@@ -52,14 +96,9 @@ __global__ __launch_bounds__(256) void strong_view_kernel(AugArgs a) {
     if (hit >= 0) {
         r = cuts[hit * 7 + 4]; g = cuts[hit * 7 + 5]; bl = cuts[hit * 7 + 6];
     } else {
-        // ---- cv2.warpAffine, INTER_LINEAR, BORDER_CONSTANT: AB_BITS 10, INTER_BITS 5, weights * 2^15
-        const double* M = a.minv + b * 6;
-        const int round_delta = 16;                                           // AB_SCALE / INTER_TAB_SIZE / 2
-        const int X0 = aug_round((M[1] * y + M[2]) * 1024.0) + round_delta, Y0 = aug_round((M[4] * y + M[5]) * 1024.0) + round_delta;
-        const int X = (X0 + aug_round(M[0] * x * 1024.0)) >> 5, Y = (Y0 + aug_round(M[3] * x * 1024.0)) >> 5;
-        const int sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31;
-        const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
         const unsigned char* base = a.src + (size_t)b * 3 * plane;
+        int sx, sy, w[4];
+        aug_warp_taps(a.minv + b * 6, x, y, sx, sy, w);
         int px[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
@@ -67,41 +106,11 @@ __global__ __launch_bounds__(256) void strong_view_kernel(AugArgs a) {
             auto at = [&](int yy, int xx) -> int {
                 return ((unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W) ? (int)p[(size_t)yy * a.W + xx] : a.border;
             };
-            const int v = w00 * at(sy, sx) + w01 * at(sy, sx + 1) + w10 * at(sy + 1, sx) + w11 * at(sy + 1, sx + 1);
+            const int v = w[0] * at(sy, sx) + w[1] * at(sy, sx + 1) + w[2] * at(sy + 1, sx) + w[3] * at(sy + 1, sx + 1);
             px[ch] = (v + (1 << 14)) >> 15;
         }
         r = px[0]; g = px[1]; bl = px[2];
-        if (a.lut) {
-            // ---- cvtColor RGB -> HSV (8 bit, H in [0,180)): integer division tables with hsv_shift = 12
-            const int v = max(max(r, g), bl), vmin = min(min(r, g), bl);
-            const int diff = v - vmin;
-            const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
-            const int sdiv = v ? aug_round((255 << 12) / (double)v) : 0;
-            const int hdiv = diff ? aug_round((180 << 12) / (6.0 * diff)) : 0;
-            const int s = (diff * sdiv + (1 << 11)) >> 12;
-            int h = (vr & (g - bl)) + (~vr & ((vg & (bl - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
-            h = (h * hdiv + (1 << 11)) >> 12;
-            h += h < 0 ? 180 : 0;
-            const unsigned char* L = a.lut + (size_t)b * 768;
-            const int h2 = L[h & 255], s2 = L[256 + s], v2 = L[512 + v];
-            // ---- cvtColor HSV -> RGB (8 bit): float sector arithmetic, cvRound to uchar
-            const float fs = s2 * (1.f / 255.f), fv = v2 * (1.f / 255.f);
-            float fr, fg, fb;
-            if (s2 == 0) {
-                fr = fg = fb = fv;
-            } else {
-                float hh = h2 * (6.f / 180.f);
-                int sector = (int)floorf(hh);
-                hh -= sector;
-                if ((unsigned)sector >= 6u) { sector = 0; hh = 0.f; }
-                const float tab[4] = {fv, fv * (1.f - fs), fv * (1.f - fs * hh), fv * (1.f - fs * (1.f - hh))};
-                const int sd[6][3] = {{1, 3, 0}, {1, 0, 2}, {3, 0, 1}, {0, 2, 1}, {0, 1, 3}, {2, 1, 0}};      // b, g, r
-                fb = tab[sd[sector][0]]; fg = tab[sd[sector][1]]; fr = tab[sd[sector][2]];
-            }
-            r = min(max(aug_round(fr * 255.f), 0), 255);
-            g = min(max(aug_round(fg * 255.f), 0), 255);
-            bl = min(max(aug_round(fb * 255.f), 0), 255);
-        }
+        if (a.lut) aug_hsv_lut(a.lut + (size_t)b * 768, r, g, bl);
     }
     unsigned char* o = a.dst + (size_t)b * 3 * plane + (size_t)oy * a.W + ox;
     o[0] = (unsigned char)r; o[plane] = (unsigned char)g; o[2 * plane] = (unsigned char)bl;
@@ -167,6 +176,245 @@ extern "C" int et_mosaic4_u8(const int64_t* tiles, uint8_t* out, int B, int S, i
     if (B <= 0 || S <= 0 || (long long)B * S * S >= (1ll << 40)) return -2;
     hipLaunchKernelGGL(mosaic4_kernel, dim3(et_cdiv((long long)B * S * S, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const long long*)tiles, out, B, S, border_value);
+    ET_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- labeled batch: mosaic + random perspective (+ mixup) + HSV + flips (LoadImagesAndLabels.__getitem__, utils/datasets.py:889-1043) --
+// The reference pastes four images into a 2S x 2S canvas (load_mosaic, :1219-1311), warps the canvas to S x S with
+// cv2.warpAffine(img4, M[:2], dsize=(S, S), borderValue=114) (random_perspective_keypoints, utils/augmentations.py:125-167; the border
+// -S/2 makes the output half the canvas), blends a second such mosaic in for mixup ((im * r + im2 * (1 - r)).astype(uint8),
+// augmentations.py:409-414), runs augment_hsv and flips.  One launch does all of it for the batch and never builds a canvas: an output
+// pixel is traced back through the flips, its four bilinear taps are fetched from a VIRTUAL canvas (the quadrant by the side of the
+// centre, tile i at (cy - y1a + y1b, cx - x1a + x1b) inside the tile's pasted rectangle, else -- the rest of the canvas and everything
+// outside it -- the border value), blended in fp64 with two rounded products and one rounded sum (this file is built without FMA
+// contraction) and truncated, colour-jittered with the helpers strong_view_kernel uses, and stored.
+// One thread makes FOUR adjacent output pixels of a row and stores one 32-bit word per plane (byte stores when S is no multiple of 4);
+// the word is assembled in OUTPUT order, so a left-right flip needs no separate reversal.  The tile table of the image sits in LDS.
+// PARITY: tile placement, matrices, ratio and LUTs are the host's (pinned on the reference, tests/golden/labeled_mosaic.npz); the warp
+// sampling and the HSV round trip restate OpenCV's published algorithms as above and are unpinned (no cv2).
+struct LmArgs {
+    const long long* tiles;     // [B][2][4][8] rows of et_mosaic4_u8: the primary mosaic and the mixup partner
+    unsigned char* dst;         // (B,3,S,S)
+    const double* minv;         // [B][2][6] dst -> src affine maps
+    const double* mix;          // [B] mixup ratio r
+    const unsigned char* lut;   // [B][3][256] or NULL
+    const int* flags;           // [B][3] has_mix, flipud, fliplr
+    int B, S;
+    int border;
+};
+
+struct LmTile {
+    const unsigned char* p;
+    int h, w, x1a, y1a, x2a, y2a, x1b, y1b;
+};
+
+__device__ __forceinline__ void lm_sample(const LmTile* T, const double* M, int x, int y, int border, int px[3]) {
+    int sx, sy, w[4];
+    aug_warp_taps(M, x, y, sx, sy, w);
+    const int xc = T[0].x2a, yc = T[0].y2a;                     // the centre (mosaic_layout)
+    int acc[3] = {1 << 14, 1 << 14, 1 << 14};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int cy = sy + (k >> 1), cx = sx + (k & 1);
+        const LmTile& t = T[(cy >= yc ? 2 : 0) + (cx >= xc ? 1 : 0)];
+        if (cx >= t.x1a && cx < t.x2a && cy >= t.y1a && cy < t.y2a) {
+            const size_t o = (size_t)(cy - t.y1a + t.y1b) * t.w + (cx - t.x1a + t.x1b), pl = (size_t)t.h * t.w;
+            acc[0] += w[k] * t.p[o]; acc[1] += w[k] * t.p[pl + o]; acc[2] += w[k] * t.p[2 * pl + o];
+        } else {
+            acc[0] += w[k] * border; acc[1] += w[k] * border; acc[2] += w[k] * border;
+        }
+    }
+    px[0] = acc[0] >> 15; px[1] = acc[1] >> 15; px[2] = acc[2] >> 15;
+}
+
+__global__ __launch_bounds__(256) void labeled_mosaic_kernel(LmArgs a) {
+    __shared__ LmTile T[8];
+    const int b = blockIdx.y;
+    if (threadIdx.x < 8) {
+        const long long* t = a.tiles + ((size_t)b * 8 + threadIdx.x) * 8;
+        LmTile& d = T[threadIdx.x];
+        d.p = (const unsigned char*)(uintptr_t)t[0];
+        d.h = (int)t[1]; d.w = (int)t[2]; d.x1a = (int)t[3]; d.y1a = (int)t[4]; d.x2a = (int)t[5]; d.y2a = (int)t[6];
+        d.x1b = (int)(t[7] >> 32); d.y1b = (int)(t[7] & 0xffffffffll);
+    }
+    __syncthreads();
+    const int S = a.S, G = (S + 3) >> 2;                       // G groups of four pixels per row
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S * G) return;
+    const int oy = i / G, ox0 = (i - oy * G) * 4;
+    const int* fl = a.flags + b * 3;
+    const int has_mix = fl[0], ud = fl[1], lr = fl[2];
+    const int y = ud ? S - 1 - oy : oy;                        // position before the flips
+    const double r = a.mix[b], omr = 1.0 - r;
+    const double* M = a.minv + (size_t)b * 12;
+    const unsigned char* L = a.lut ? a.lut + (size_t)b * 768 : nullptr;
+    unsigned word[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int ox = ox0 + j;
+        if (ox < S) {
+            const int x = lr ? S - 1 - ox : ox;
+            int px[3];
+            lm_sample(T, M, x, y, a.border, px);
+            if (has_mix) {
+                int qx[3];
+                lm_sample(T + 4, M + 6, x, y, a.border, qx);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) px[c] = (int)((double)px[c] * r + (double)qx[c] * omr);       // astype(uint8): truncation
+            }
+            if (L) aug_hsv_lut(L, px[0], px[1], px[2]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) word[c] |= (unsigned)px[c] << (8 * j);
+        }
+    }
+    const size_t plane = (size_t)S * S;
+    unsigned char* o = a.dst + (size_t)b * 3 * plane + (size_t)oy * S + ox0;
+    if ((S & 3) == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *(unsigned*)(o + c * plane) = word[c];
+    } else {
+        for (int j = 0; j < 4 && ox0 + j < S; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c * plane + j] = (unsigned char)(word[c] >> (8 * j));
+    }
+}
+
+extern "C" int et_labeled_mosaic_u8(const int64_t* tiles, const double* minv, const double* mix, const uint8_t* lut, const int* flags,
+                                    uint8_t* out, int B, int S, int border_value, et_stream_t stream) {
+    if (!tiles || !minv || !mix || !flags || !out) return -1;
+    if (B <= 0 || B > 65535 || S <= 0 || S > 16384) return -2;
+    if (((uintptr_t)out & 3) != 0) return -3;                   // the 32-bit stores
+    LmArgs a;
+    a.tiles = (const long long*)tiles; a.dst = out; a.minv = minv; a.mix = mix; a.lut = lut; a.flags = flags;
+    a.B = B; a.S = S; a.border = border_value;
+    hipLaunchKernelGGL(labeled_mosaic_kernel, dim3(et_cdiv((long long)S * ((S + 3) >> 2), 256), B), dim3(256), 0, (hipStream_t)stream, a);
+    ET_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- labels of the labeled batch ---------------------------------------------------------------------------------------------------
+// Per source label, with the reference's dtypes (labels are float32; numpy treats the Python scalars w, h, padw, padh, s, eps as weak,
+// so they enter float32 expressions as float32): xywhn2xyxy(w, h, padw, padh) in float32 (utils/general.py:640), the four corners
+// times M in fp64, min / max, clip to [0, S] (augmentations.py:181-193), box_candidates(box1 = xyxy_f32 * s, box2, area_thr 0.10)
+// (:261, :417-422), the new box assigned back to float32, xyxy2xywhn(w = h = S, clip to S - 1e-3) (general.py:649-658), the flips as
+// 1 - v, clip(0, 1) (datasets.py:1027).  Output rows [img, cls, x, y, w, h] in the reference's order: images ascending (collate_fn),
+// inside an image the primary mosaic's tiles in tile order and then the partner's, survivors in source order.  The order comes from a
+// stable scan, not from atomics: one workgroup per image walks the image's rows 256 at a time, scans the keep flags and writes the
+// survivors to `tmp` at the image's own row range; a second launch sums the counts of the images in front (B is a batch size: every
+// workgroup reads at most B counts) and copies each image's survivors to their place.  The capacity of `out` is L_in: no overflow.
+// table [B][2][4][6] int32 = {row0, row1, h, w, padw, padh} per (image, mosaic, tile): rows [row0, row1) of `labels`; the ranges
+// ascend without gaps inside an image and do not overlap between images (the binding checks this before the launch).
+struct LtArgs {
+    const float* labels;        // (L,5) cls, x, y, w, h normalised to the source image
+    const int* table;
+    const double* M;            // [B][2][9]
+    const double* s;            // [B][2]
+    const int* flags;           // [B][3] has_mix, flipud, fliplr
+    float* tmp;                 // (L,6)
+    int* counts;                // [B]
+    int B, S, L;
+};
+
+__global__ __launch_bounds__(256) void labeled_targets_kernel(LtArgs a) {
+    __shared__ int tab[48];
+    __shared__ int wsum[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 48) tab[tid] = a.table[b * 48 + tid];
+    __syncthreads();
+    const int r0 = max(tab[0], 0), r1 = min(tab[7 * 6 + 1], a.L);
+    const int ud = a.flags[b * 3 + 1], lr = a.flags[b * 3 + 2];
+    const float S = (float)a.S, hi = (float)((double)a.S - 1e-3);
+    int run = 0;
+    for (int base = r0; base < r1; base += 256) {
+        const int row = base + tid;
+        int keep = 0, k = -1;
+        float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        if (row < r1)
+            for (int q = 0; q < 8; ++q)
+                if (row >= tab[q * 6] && row < tab[q * 6 + 1]) k = q;
+        if (k >= 0) {
+            const float* lb = a.labels + (size_t)row * 5;
+            const float fw = (float)tab[k * 6 + 3], fh = (float)tab[k * 6 + 2], pw = (float)tab[k * 6 + 4], ph = (float)tab[k * 6 + 5];
+            const float x1 = fw * (lb[1] - lb[3] / 2) + pw, y1 = fh * (lb[2] - lb[4] / 2) + ph;
+            const float x2 = fw * (lb[1] + lb[3] / 2) + pw, y2 = fh * (lb[2] + lb[4] / 2) + ph;
+            const double* M = a.M + ((size_t)b * 2 + (k >> 2)) * 9;
+            const double X[4] = {x1, x2, x1, x2}, Y[4] = {y1, y2, y2, y1};
+            double xmin = 0, xmax = 0, ymin = 0, ymax = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const double u = X[c] * M[0] + Y[c] * M[1] + M[2], v = X[c] * M[3] + Y[c] * M[4] + M[5];
+                xmin = c ? fmin(xmin, u) : u; xmax = c ? fmax(xmax, u) : u;
+                ymin = c ? fmin(ymin, v) : v; ymax = c ? fmax(ymax, v) : v;
+            }
+            const double dS = (double)a.S;
+            xmin = fmin(fmax(xmin, 0.0), dS); xmax = fmin(fmax(xmax, 0.0), dS);
+            ymin = fmin(fmax(ymin, 0.0), dS); ymax = fmin(fmax(ymax, 0.0), dS);
+            const float sf = (float)a.s[b * 2 + (k >> 2)];
+            const float w1 = x2 * sf - x1 * sf, h1 = y2 * sf - y1 * sf;
+            const double w2 = xmax - xmin, h2 = ymax - ymin;
+            const double ar = fmax(w2 / (h2 + 1e-16), h2 / (w2 + 1e-16));
+            const float den = w1 * h1 + 1e-16f;
+            keep = (w2 > 2.0) && (h2 > 2.0) && (w2 * h2 / (double)den > 0.1) && (ar < 20.0);
+            const float a0 = fminf(fmaxf((float)xmin, 0.f), hi), a1 = fminf(fmaxf((float)ymin, 0.f), hi);
+            const float a2 = fminf(fmaxf((float)xmax, 0.f), hi), a3 = fminf(fmaxf((float)ymax, 0.f), hi);
+            float cx = ((a0 + a2) / 2) / S, cy = ((a1 + a3) / 2) / S;
+            const float bw = (a2 - a0) / S, bh = (a3 - a1) / S;
+            if (ud) cy = 1 - cy;
+            if (lr) cx = 1 - cx;
+            o[0] = lb[0];
+            o[1] = fminf(fmaxf(cx, 0.f), 1.f); o[2] = fminf(fmaxf(cy, 0.f), 1.f);
+            o[3] = fminf(fmaxf(bw, 0.f), 1.f); o[4] = fminf(fmaxf(bh, 0.f), 1.f);
+        }
+        int inc = keep;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(inc, d);
+            if (lane >= d) inc += up;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int woff = 0;
+        for (int w = 0; w < wave; ++w) woff += wsum[w];
+        const int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (keep) {
+            float* d = a.tmp + (size_t)(r0 + run + woff + inc - 1) * 6;
+            d[0] = (float)b; d[1] = o[0]; d[2] = o[1]; d[3] = o[2]; d[4] = o[3]; d[5] = o[4];
+        }
+        run += tot;
+        __syncthreads();
+    }
+    if (tid == 0) a.counts[b] = run;
+}
+
+__global__ __launch_bounds__(256) void labeled_targets_compact_kernel(const float* __restrict__ tmp, const int* __restrict__ counts,
+                                                                      const int* __restrict__ table, float* __restrict__ out,
+                                                                      int* __restrict__ n_out, int B) {
+    __shared__ int wsum[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int part = 0;
+    for (int i = tid; i < b; i += 256) part += counts[i];
+    part = et_wave_sum_i(part);
+    if ((tid & 63) == 0) wsum[tid >> 6] = part;
+    __syncthreads();
+    const int off = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const int cnt = counts[b], r0 = table[b * 48];
+    for (int i = tid; i < cnt * 6; i += 256) out[(size_t)off * 6 + i] = tmp[(size_t)r0 * 6 + i];
+    if (b == B - 1 && tid == 0) *n_out = off + cnt;
+}
+
+extern "C" int et_labeled_mosaic_targets(const float* labels, int L_in, const int* table, const double* M, const double* s,
+                                         const int* flags, int B, int S, float* tmp, int* counts, float* out, int* n_out,
+                                         et_stream_t stream) {
+    if (!labels || !table || !M || !s || !flags || !tmp || !counts || !out || !n_out) return -1;
+    if (B <= 0 || S <= 0 || L_in <= 0 || L_in > (1 << 28)) return -2;
+    LtArgs a;
+    a.labels = labels; a.table = table; a.M = M; a.s = s; a.flags = flags; a.tmp = tmp; a.counts = counts;
+    a.B = B; a.S = S; a.L = L_in;
+    hipLaunchKernelGGL(labeled_targets_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+    ET_CHECK_LAUNCH();
+    hipLaunchKernelGGL(labeled_targets_compact_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const float*)tmp, (const int*)counts,
+                       table, out, n_out, B);
     ET_CHECK_LAUNCH();
     return 0;
 }

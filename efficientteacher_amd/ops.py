@@ -1342,6 +1342,85 @@ def mosaic4_u8(tiles, layouts, s, border_value=114):
     return out
 
 
+def labeled_tile_table(tiles, layouts, s):
+    """the (B, 2, 4, 8) int64 tile table of et_labeled_mosaic_u8 as ONE numpy array: tiles[b][m] = the four uint8 (3, h, w) device tensors
+    of mosaic m of image b in tile order (m = 0 the primary, m = 1 the mixup partner, or None), layouts[b][m] = their mosaic_layout rows.
+    Every pasted rectangle is checked against its tile and the canvas here: the kernel reads the tile wherever the table says"""
+    import numpy as np
+    B = len(tiles)
+    table = np.zeros((B, 2, 4, 8), np.int64)
+    dev = None
+    for b in range(B):
+        assert len(tiles[b]) == 2 and tiles[b][0] is not None
+        for m in range(2):
+            if tiles[b][m] is None:
+                continue
+            assert len(tiles[b][m]) == 4 and len(layouts[b][m]) == 4
+            for i, (t, row) in enumerate(zip(tiles[b][m], layouts[b][m])):
+                dev = t.device if dev is None else dev
+                assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[0] == 3 and t.is_contiguous() and t.device == dev
+                x1a, y1a, x2a, y2a, x1b, y1b = (int(v) for v in row[:6])
+                table[b, m, i] = (t.data_ptr(), t.shape[1], t.shape[2], x1a, y1a, x2a, y2a, (x1b << 32) | (y1b & 0xffffffff))
+    h, w, x1a, y1a, x2a, y2a = (table[..., k] for k in range(1, 7))
+    x1b, y1b = table[..., 7] >> 32, table[..., 7] & 0xffffffff
+    dx, dy = np.maximum(x2a - x1a, 0), np.maximum(y2a - y1a, 0)
+    ok = (x1a >= 0) & (y1a >= 0) & (x2a <= 2 * s) & (y2a <= 2 * s) & (x1b >= 0) & (y1b >= 0) & (x1b + dx <= w) & (y1b + dy <= h)
+    if not bool(ok.all()):
+        raise ValueError(f"labeled_tile_table: a pasted rectangle leaves its tile or the {2 * s} x {2 * s} canvas: rows {np.argwhere(~ok).tolist()}")
+    return table
+
+
+def labeled_mosaic_u8(tiles, layouts, minv, mix, lut, flags, s, border_value=114):
+    """The labeled batch's pixels in one launch (csrc/augment.hip et_labeled_mosaic_u8): tiles / layouts as labeled_tile_table takes
+    them; minv (B,2,6) fp64 dst->src maps of the two mosaics, mix (B,) fp64 mixup ratios, lut (B,3,256) uint8 or None, flags (B,3)
+    int32 (has_mix, flipud, fliplr), all on the device.  -> (B, 3, s, s) uint8 RGB planes"""
+    B = len(tiles)
+    table = labeled_tile_table(tiles, layouts, int(s))
+    dev = minv.device
+    assert minv.dtype == torch.float64 and minv.shape == (B, 2, 6) and mix.dtype == torch.float64 and mix.shape == (B,)
+    assert flags.dtype == torch.int32 and flags.shape == (B, 3) and (lut is None or (lut.dtype == torch.uint8 and lut.shape == (B, 3, 256)))
+    assert all(tiles[b][0][0].device == dev for b in range(B))
+    tdev = torch.from_numpy(table).to(dev, non_blocking=True)
+    out = torch.empty((B, 3, int(s), int(s)), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().et_labeled_mosaic_u8(_lib.ptr(tdev), _lib.ptr(minv.contiguous()), _lib.ptr(mix.contiguous()),
+                                                _lib.ptr(lut.contiguous()) if lut is not None else None, _lib.ptr(flags.contiguous()),
+                                                _lib.ptr(out), B, int(s), int(border_value), _lib.stream(out)), "et_labeled_mosaic_u8")
+    return out
+
+
+def labeled_mosaic_targets(labels, table, M, scale, flags, s):
+    """The labeled batch's targets (csrc/augment.hip et_labeled_mosaic_targets).  labels (L_in,5) float32 [cls, x, y, w, h] of every tile
+    of every mosaic, concatenated; table (B,2,4,6) int32 NUMPY array {row0, row1, h, w, padw, padh} (checked here, then copied); M
+    (B,2,9) fp64, scale (B,2) fp64, flags (B,3) int32 on the device.  -> (out (L_in,6) float32 whose first n rows are the reference's
+    collated [img, cls, x, y, w, h], n (1,) int32 on the device): the caller narrows out by n when it may read it"""
+    import numpy as np
+    L, B = int(labels.shape[0]), int(M.shape[0])
+    dev = M.device
+    assert labels.dtype == torch.float32 and labels.dim() == 2 and labels.shape[1] == 5 and (L == 0 or labels.device == dev)
+    assert isinstance(table, np.ndarray) and table.dtype == np.int32 and table.shape == (B, 2, 4, 6)
+    assert M.dtype == torch.float64 and M.shape == (B, 2, 9) and scale.dtype == torch.float64 and scale.shape == (B, 2)
+    assert flags.dtype == torch.int32 and flags.shape == (B, 3)
+    flat = table.reshape(B, 8, 6)
+    bounds = np.concatenate((flat[:, :, 0].reshape(-1), [L]))           # row0 of every slot in order, then the end
+    ok = (flat[:, :, 0] >= 0).all() and (flat[:, :, 1] >= flat[:, :, 0]).all() and (flat[:, :, 1] <= L).all() \
+        and (flat[:, :-1, 1] == flat[:, 1:, 0]).all() and (np.diff(bounds) >= 0).all() and (flat[:-1, 7, 1] <= flat[1:, 0, 0]).all()
+    if not ok:
+        raise ValueError("labeled_mosaic_targets: the row ranges of the table must ascend without gaps inside an image, not overlap "
+                         f"between images and stay inside the {L} label rows")
+    out = torch.empty((L, 6), dtype=torch.float32, device=dev)
+    n = torch.zeros(1, dtype=torch.int32, device=dev)
+    if L == 0:
+        return out, n
+    tmp = torch.empty((L, 6), dtype=torch.float32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    tdev = torch.from_numpy(np.ascontiguousarray(table)).to(dev, non_blocking=True)
+    _lib.check(_lib.load().et_labeled_mosaic_targets(_lib.ptr(labels.contiguous()), L, _lib.ptr(tdev), _lib.ptr(M.contiguous()),
+                                                     _lib.ptr(scale.contiguous()), _lib.ptr(flags.contiguous()), B, int(s), _lib.ptr(tmp),
+                                                     _lib.ptr(counts), _lib.ptr(out), _lib.ptr(n), _lib.stream(out)),
+               "et_labeled_mosaic_targets")
+    return out, n
+
+
 def tal_targets_pad(targets, B, img_w, img_h):
     """ComputeTalLoss.preprocess on the device: (n,6) [img, cls, x, y, w, h] normalised -> gt_labels (B,G,1), gt_bboxes (B,G,4) xyxy
     pixels, mask_gt (B,G,1).  G = max(n, 1) without a host synchronisation while n <= 32 * B (the reference loops over

@@ -23,8 +23,11 @@ from .. import ops
 MAX_CUT = 32
 
 
-def affine_matrix(h, w, degrees, translate, scale, shear, rng=random):
-    """(M (3,3), s): datasets_ssod.py:909-938 with perspective = 0 and no border"""
+def affine_matrix(h, w, degrees, translate, scale, shear, rng=random, out_hw=None):
+    """(M (3,3), s): datasets_ssod.py:909-938 with perspective = 0.  (h, w) is the size of the image that is warped: C centres it.
+    out_hw = (height, width) of the OUTPUT when a border changes it (random_perspective_keypoints, augmentations.py:130-159: the
+    mosaic's 2s x 2s canvas comes out s x s) -- T translates by the output size; None = no border, the same size"""
+    oh, ow = (h, w) if out_hw is None else out_hw
     C = np.eye(3)
     C[0, 2] = -w / 2
     C[1, 2] = -h / 2
@@ -39,8 +42,8 @@ def affine_matrix(h, w, degrees, translate, scale, shear, rng=random):
     S[0, 1] = math.tan(rng.uniform(-shear, shear) * math.pi / 180)
     S[1, 0] = math.tan(rng.uniform(-shear, shear) * math.pi / 180)
     T = np.eye(3)
-    T[0, 2] = rng.uniform(0.5 - translate, 0.5 + translate) * w
-    T[1, 2] = rng.uniform(0.5 - translate, 0.5 + translate) * h
+    T[0, 2] = rng.uniform(0.5 - translate, 0.5 + translate) * ow
+    T[1, 2] = rng.uniform(0.5 - translate, 0.5 + translate) * oh
     return T @ S @ R @ C, s
 
 
@@ -188,3 +191,173 @@ class MosaicGenerator:
         layout = mosaic_layout(self.s, yc, xc, shapes)
         out = ops.mosaic4_u8([tiles], [layout], self.s)[0]
         return out, mosaic_labels(self.s, layout, shapes, [labels[i] for i in four])
+
+
+# ---- the labeled batch (LoadImagesAndLabels.__getitem__'s mosaic branch, utils/datasets.py:889-1043) -----------------------------------
+class PendingLabeledBatch:
+    """A labeled batch whose kernels have been launched.  `event` (None for the emulator's CPU tensors) is recorded behind them and behind the
+    copy of the row count n to pinned memory; result() waits for it on the HOST -- the one host read of n -- narrows the targets to
+    (n, 6) and makes the consumer's current stream wait for the event"""
+
+    def __init__(self, imgs, out, n_dev, n_host, paths, event, stream):
+        self.imgs, self.out, self.n_dev, self.n_host, self.paths, self.event, self.stream = imgs, out, n_dev, n_host, paths, event, stream
+
+    def result(self):
+        if self.n_host is None:                                # emulator / CPU tensors
+            n = int(self.n_dev[0])
+        else:
+            self.event.synchronize()
+            n = int(self.n_host[0])
+            if self.stream is not None:
+                cur = torch.cuda.current_stream(self.imgs.device)
+                cur.wait_event(self.event)
+                self.imgs.record_stream(cur)
+                self.out.record_stream(cur)
+        return self.imgs, self.out[:n], self.paths, (None,) * self.imgs.shape[0]
+
+
+class LabeledBatchGenerator:
+    """The labeled stream's batches on the device.  The host keeps the reference's random recipe -- sample() consumes `random` and
+    `np.random` exactly as __getitem__'s mosaic branch does: the mosaic gate, load_mosaic (centre, three partners, shuffle,
+    random_perspective_keypoints' eight draws with C from the 2s canvas and T from the s output), the mixup gate and, behind it,
+    randint, a second mosaic and np.random.beta(32, 32), the HSV gains, the two flips -- and two kernels do the work
+    (csrc/augment.hip): et_labeled_mosaic_u8 the pixels, et_labeled_mosaic_targets the labels.
+    PARITY: recipe, random streams, canvas, matrices, ratio, LUTs and labels are pinned on the live reference
+    (tests/golden/labeled_mosaic.npz); the warp sampling and the HSV round trip restate OpenCV's published algorithms (no cv2).
+    cfg: the reference's config node (cfg.hyp, cfg.Dataset.img_size / np / num_ids); n: the number of images of the dataset.
+    What the kernels do not cover raises NotImplementedError here, and the caller keeps the reference's loader for it."""
+
+    def __init__(self, cfg, n, seed=None, stream=None, rect=False, image_weights=False):
+        hyp, ds = cfg.hyp, cfg.Dataset
+        g = lambda node, k, d=0: (node.get(k, d) if hasattr(node, "get") else getattr(node, k, d))
+        if float(g(hyp, "perspective", 0.0)) != 0:
+            raise NotImplementedError("LabeledBatchGenerator: hyp.perspective != 0 needs cv2.warpPerspective's projective sampling; "
+                                      "the kernel implements the affine warp of every shipped recipe")
+        if float(g(hyp, "copy_paste", 0.0)) > 0:
+            raise NotImplementedError("LabeledBatchGenerator: hyp.copy_paste > 0 needs segment masks, which the device path does not hold")
+        if int(g(ds, "np", 0)) > 0:
+            raise NotImplementedError("LabeledBatchGenerator: Dataset.np > 0 (keypoint labels) is not transformed on the device")
+        if int(g(ds, "num_ids", 0)) > 0:
+            raise NotImplementedError("LabeledBatchGenerator: Dataset.num_ids > 0 (with_id: a tracking id per label) is not carried on the device")
+        if rect:
+            raise NotImplementedError("LabeledBatchGenerator: rect batches take the letterbox branch, which stays with the reference's loader")
+        if image_weights:
+            raise NotImplementedError("LabeledBatchGenerator: image_weights re-draws the index list per epoch on the host; not supported")
+        if float(g(hyp, "mosaic", 1.0)) < 1:
+            raise NotImplementedError("LabeledBatchGenerator: hyp.mosaic < 1 sends some images through the letterbox branch, which stays "
+                                      "with the reference's loader")
+        self.hyp, self.s, self.n = hyp, int(ds.img_size), int(n)
+        self._g = g
+        self.indices = range(self.n)
+        self.border = [-self.s // 2, -self.s // 2]                # datasets.py:651
+        self.mosaic = True                                       # the trainer sets dataset.mosaic = False for the last no_aug_epochs
+        self.py_rng = random.Random(seed)
+        self.np_rng = np.random.RandomState(seed)
+        self.stream = stream
+
+    def _mosaic(self, index):
+        """load_mosaic's draws (datasets.py:1223-1225, augmentations.py:140-159) -> (yc, xc, four, M, s)"""
+        s, hyp, g = self.s, self.hyp, self._g
+        yc, xc = [int(self.py_rng.uniform(-x, 2 * s + x)) for x in self.border]
+        four = [index] + self.py_rng.choices(self.indices, k=3)
+        self.py_rng.shuffle(four)
+        M, sc = affine_matrix(2 * s, 2 * s, g(hyp, "degrees"), g(hyp, "translate"), g(hyp, "scale"), g(hyp, "shear"), self.py_rng,
+                              out_hw=(2 * s + 2 * self.border[0], 2 * s + 2 * self.border[1]))
+        return yc, xc, four, M, sc
+
+    def sample(self, index):
+        """host side of one image: {'mosaics': [(yc, xc, four, M, s)] * (1 or 2), 'r': mixup ratio or None, 'lut': (3,256) u8 or None,
+        'flipud', 'fliplr'}"""
+        hyp, g = self.hyp, self._g
+        if not self.mosaic:
+            raise NotImplementedError("LabeledBatchGenerator: the mosaic is closed (no_aug_epochs): the letterbox branch stays with the "
+                                      "reference's loader")
+        index = self.indices[index]
+        self.py_rng.random()                                     # the mosaic gate (hyp.mosaic = 1: always taken)
+        mosaics = [self._mosaic(index)]
+        r = None
+        if self.py_rng.random() < g(hyp, "mixup", 0.0):
+            mosaics.append(self._mosaic(self.py_rng.randint(0, self.n - 1)))
+            r = float(self.np_rng.beta(32.0, 32.0))
+        hs = (g(hyp, "hsv_h", 0.0), g(hyp, "hsv_s", 0.0), g(hyp, "hsv_v", 0.0))
+        lut = hsv_luts(*hs, self.np_rng) if any(hs) else None
+        ud = self.py_rng.random() < g(hyp, "flipud", 0.0)
+        lr = self.py_rng.random() < g(hyp, "fliplr", 0.0)
+        return dict(mosaics=mosaics, r=r, lut=lut, flipud=bool(ud), fliplr=bool(lr))
+
+    def launch(self, images, labels, indices, paths=None):
+        """sample every image of the batch and launch the two kernels (on self.stream when given) -> PendingLabeledBatch"""
+        from .. import ops
+        s, B = self.s, len(indices)
+        samples = [self.sample(int(i)) for i in indices]
+        use_lut = any(sm["lut"] is not None for sm in samples)
+        f64 = np.zeros(B * 33)                                   # one staging array: minv (B,2,6) | M (B,2,9) | s (B,2) | mix (B,)
+        minv, M, sc, mix = (f64[:B * 12].reshape(B, 2, 6), f64[B * 12:B * 30].reshape(B, 2, 9), f64[B * 30:B * 32].reshape(B, 2),
+                            f64[B * 32:])
+        minv[:] = [1, 0, 0, 0, 1, 0]; M[:] = np.eye(3).reshape(9); sc[:] = 1.0; mix[:] = 1.0
+        flags = np.zeros((B, 3), np.int32)
+        lut = np.tile(np.arange(256, dtype=np.uint8), (B, 3, 1)) if use_lut else None
+        ltab = np.zeros((B, 2, 4, 6), np.int32)
+        tiles, layouts, rows, row = [], [], [], 0
+        for b, sm in enumerate(samples):
+            tb, lb = [None, None], [None, None]
+            for m in range(2):
+                if m < len(sm["mosaics"]):
+                    yc, xc, four, Mm, sm_s = sm["mosaics"][m]
+                    tb[m] = [images[i] for i in four]
+                    shapes = [(int(t.shape[1]), int(t.shape[2])) for t in tb[m]]
+                    lb[m] = mosaic_layout(s, yc, xc, shapes)
+                    minv[b, m], M[b, m], sc[b, m] = invert_affine(Mm), Mm.reshape(-1), sm_s
+                    for k, (i, (h, w), lay) in enumerate(zip(four, shapes, lb[m])):
+                        lab = np.asarray(labels[i], dtype=np.float32).reshape(-1, 5)
+                        ltab[b, m, k] = (row, row + lab.shape[0], h, w, lay[6], lay[7])
+                        rows.append(lab)
+                        row += lab.shape[0]
+                else:
+                    ltab[b, m, :, :2] = row
+            tiles.append(tb); layouts.append(lb)
+            flags[b] = (len(sm["mosaics"]) == 2, sm["flipud"], sm["fliplr"])
+            if sm["r"] is not None:
+                mix[b] = sm["r"]
+            if sm["lut"] is not None:
+                lut[b] = sm["lut"]
+        lab_all = np.concatenate(rows, 0) if rows else np.zeros((0, 5), np.float32)
+        dev = tiles[0][0][0].device
+        cuda = dev.type == "cuda"
+        side = self.stream if cuda else None
+        import contextlib
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream(dev))     # the source images were written on the caller's stream
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            t = lambda a: torch.from_numpy(a).to(dev, non_blocking=True)
+            d64 = t(f64)
+            dflags = t(flags)
+            imgs = ops.labeled_mosaic_u8(tiles, layouts, d64[:B * 12].view(B, 2, 6), d64[B * 32:], t(lut) if use_lut else None, dflags, s)
+            out, n_dev = ops.labeled_mosaic_targets(t(lab_all), ltab, d64[B * 12:B * 30].view(B, 2, 9), d64[B * 30:B * 32].view(B, 2),
+                                                    dflags, s)
+            n_host = event = None
+            if cuda:
+                n_host = torch.empty(1, dtype=torch.int32).pin_memory()
+                n_host.copy_(n_dev, non_blocking=True)
+                event = torch.cuda.Event()
+                event.record(torch.cuda.current_stream(dev))
+        return PendingLabeledBatch(imgs, out, n_dev, n_host, tuple(indices) if paths is None else tuple(paths[i] for i in indices),
+                                   event, side)
+
+    def __call__(self, images, labels, indices, paths=None):
+        """images: index -> (3, h, w) uint8 device tensor with max(h, w) <= img_size (what load_image returns, as RGB planes); labels:
+        index -> (n, 5) float32 [cls, x, y, w, h] normalised; indices: the dataset indices of this batch.  -> the reference's batch tuple
+        (imgs (B,3,s,s) uint8, targets (n,6) float32 [img, cls, x, y, w, h], paths, shapes = (None,) * B), tensors on the device"""
+        return self.launch(images, labels, indices, paths).result()
+
+    def batches(self, images, labels, index_batches, paths=None):
+        """the `labeled` iterable of Trainer / SSODTrainer.train_with_unlabeled: batch k + 1 is launched before batch k is handed out, so
+        with stream= its kernels run beside the step that consumes batch k"""
+        pending = None
+        for idx in index_batches:
+            nxt = self.launch(images, labels, list(idx), paths)
+            if pending is not None:
+                yield pending.result()
+            pending = nxt
+        if pending is not None:
+            yield pending.result()

@@ -31,7 +31,7 @@ enum { ET_F32 = 0, ET_BF16 = 1, ET_F16 = 2 };   /* ET_F16 (r05): IEEE half stora
  * for ("gfx950") and the ABI version.  ET_ABI_VERSION changes whenever an entry point is added or a signature / workspace
  * contract changes; a binding must refuse a library whose et_abi_version() differs from the header it was written against
  * (efficientteacher_amd/_lib.py does): a stale libet_hip.so would otherwise read e.g. a new int argument as the stream. */
-#define ET_ABI_VERSION 11
+#define ET_ABI_VERSION 12
 const char* et_build_arch(void);
 int et_abi_version(void);
 
@@ -394,6 +394,27 @@ int et_strong_view_u8(const uint8_t* weak, uint8_t* strong, int B, int H, int W,
  * planes, h, w, x1a, y1a, x2a, y2a, x1b << 32 | y1b}: canvas rectangle and its origin inside the image, tile order top-left,
  * top-right, bottom-left, bottom-right (x2a / y2a of tile 0 = the centre).  Host recipe: efficientteacher_amd/utils/augment.py. */
 int et_mosaic4_u8(const int64_t* tiles, uint8_t* out, int B, int S, int border_value, et_stream_t stream);
+/* The LABELED batch of LoadImagesAndLabels.__getitem__'s mosaic branch (utils/datasets.py:889-1043) in one launch: out (B, 3, S, S) uint8
+ * RGB planes = flips(augment_hsv(mixup(warp(mosaic A), warp(mosaic B)))) where warp is cv2.warpAffine(canvas 2S x 2S, M[:2],
+ * dsize = (S, S), borderValue) of random_perspective_keypoints (utils/augmentations.py:125-167) sampled straight from the tiles -- no
+ * canvas is built -- and mixup is (uint8)(a * r + b * (1 - r)) in fp64 (augmentations.py:409-414), applied where has_mix is set.
+ * tiles: DEVICE table [B][2][4][8] int64, rows as et_mosaic4_u8's ([b][0] the primary mosaic, [b][1] the partner, ignored without
+ * mixup); every pasted rectangle must lie inside its tile (x1b + x2a - x1a <= w, y1b + y2a - y1a <= h) and inside the canvas: the
+ * kernel reads the tile wherever the rectangle says.  minv [B][2][6] fp64 dst->src maps; mix [B] fp64 the ratio r; lut [B][3][256]
+ * uint8 or NULL; flags [B][3] int32 (has_mix, flipud, fliplr).  out must be 4-byte aligned.  PARITY: the host recipe is pinned on the
+ * reference (tests/golden/labeled_mosaic.npz); warp sampling and HSV restate OpenCV's published 8-bit algorithms (unpinned, no cv2). */
+int et_labeled_mosaic_u8(const int64_t* tiles, const double* minv, const double* mix, const uint8_t* lut, const int* flags,
+                         uint8_t* out, int B, int S, int border_value, et_stream_t stream);
+/* The labels of that batch: labels (L_in, 5) float32 [cls, x, y, w, h] normalised to their source image, concatenated in the order
+ * image, mosaic, tile; table [B][2][4][6] int32 {row0, row1, h, w, padw, padh}: rows [row0, row1) belong to that tile, the ranges
+ * ascend without gaps inside an image and do not overlap between images (an absent partner has row0 == row1); M [B][2][9] fp64 the
+ * forward matrices, s [B][2] fp64 their scales, flags as above.  Arithmetic in the reference's dtypes: xywhn2xyxy in float32, corners
+ * times M in fp64, clip to [0, S], box_candidates (area_thr 0.10), xyxy2xywhn with its clip to S - 1e-3 in float32, flips, clip(0, 1).
+ * out (L_in, 6) float32 rows [img, cls, x, y, w, h], COMPACTED in the reference's order (images ascending; primary tiles, then the
+ * partner's; survivors in source order: a stable scan, no atomics); *n_out (device int32) = the number of rows written (<= L_in, so
+ * no overflow).  tmp (L_in, 6) float32 and counts [B] int32 are scratch.  L_in > 0.                                                   */
+int et_labeled_mosaic_targets(const float* labels, int L_in, const int* table, const double* M, const double* s, const int* flags,
+                              int B, int S, float* tmp, int* counts, float* out, int* n_out, et_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Online pseudo labels.  Replaces FairPseudoLabel.create_pseudo_label_online_with_gt
