@@ -82,6 +82,8 @@ SIGNATURES = {
     "et_mosaic4_u8": (c_int, [P, P, c_int, c_int, c_int, P]),
     "et_labeled_mosaic_u8": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "et_labeled_mosaic_targets": (c_int, [P, c_int, P, P, P, P, c_int, c_int, P, P, P, P, P]),
+    "et_letterbox_u8": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "et_letterbox_targets": (c_int, [P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
     "et_pseudo_label_transform": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "et_score_log_append": (c_int, [P, P, c_int, c_int, P, P, P, c_int64, P]),
     "et_pseudo_quality_workspace_bytes": (c_int, [c_int, ctypes.POINTER(c_size_t)]),

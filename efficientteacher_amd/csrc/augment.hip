@@ -418,3 +418,271 @@ extern "C" int et_labeled_mosaic_targets(const float* labels, int L_in, const in
     ET_CHECK_LAUNCH();
     return 0;
 }
+
+// ---- letterbox batch: the OTHER branch of LoadImagesAndLabels.__getitem__ (utils/datasets.py:904-953) -------------------------------
+// load_image -> letterbox(auto=False) (utils/augmentations.py:92-123: cv2.resize to new_unpad when it differs from the image, then
+// copyMakeBorder with 114) -> with augment, random_perspective_keypoints' cv2.warpAffine(im, M[:2], dsize = (W, H), borderValue 114)
+// (:125-167, no border argument: the output has the canvas's size), augment_hsv, flips.  Validation (rect, augment = False) takes only
+// the resize and the border.  One launch per batch and no canvas: an output pixel is traced back through the flips; with has_warp its
+// four bilinear taps are fetched from a VIRTUAL H x W canvas -- 114 outside the canvas (the warp's borderValue), 114 inside the
+// letterbox border (copyMakeBorder's colour), the letterboxed image inside [left, left + nw) x [top, top + nh) -- and without it the
+// pixel is the canvas pixel itself.  The letterboxed image is the source pixel when (nw, nh) == (w, h): the common case after
+// load_image, a pad without interpolation, exact by construction.  Otherwise it is cv2.resize(im, (nw, nh), INTER_LINEAR) computed on
+// the fly from four source pixels: OpenCV's 8-bit path (resize.cpp) -- per axis scale = 1 / ((double)dst / src),
+// f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s, clamped to the first / last source pixel with f = 0, coefficients
+// cvRound((1 - f) * 2048) and cvRound(f * 2048) as shorts; horizontal pass in int32, vertical pass
+// (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.  At an exact 2:1 ratio that is (a + b + c + d + 2) >> 2, what
+// mosaic4_kernel computes.  One thread makes four adjacent pixels of a row and stores one 32-bit word per plane, as
+// labeled_mosaic_kernel does; W % 4 == 0 is demanded (every letterbox shape is a multiple of the stride), H != W is allowed.
+// table [B][8] int64 = {device pointer of the (3, h, w) uint8 planes, h, w, nw, nh, left, top, 0}.
+// PARITY: geometry, matrices and LUTs are the host's (pinned on the reference, tests/golden/letterbox.npz); the resize, the warp
+// sampling and the HSV round trip restate OpenCV's published 8-bit algorithms and are unpinned (no cv2).
+struct LbArgs {
+    const long long* table;     // [B][8]
+    unsigned char* dst;         // (B,3,H,W)
+    const double* minv;         // [B][6] dst -> src affine map
+    const unsigned char* lut;   // [B][3][256] or NULL
+    const int* flags;           // [B][3] has_warp, flipud, fliplr
+    int B, H, W;
+    int border;
+};
+
+struct LbImage {
+    const unsigned char* p;
+    int h, w, nw, nh, left, top;
+};
+
+// one axis of cv2.resize INTER_LINEAR, 8 bit: destination index d of `dst` from `src` pixels -> first source index and the two coefficients
+__device__ __forceinline__ void lb_resize_coef(int d, int dst, int src, int& s0, int& c0, int& c1) {
+    const double scale = 1.0 / ((double)dst / (double)src);
+    float f = (float)((d + 0.5) * scale - 0.5);
+    int s = (int)floorf(f);
+    f -= (float)s;
+    if (s < 0) { s = 0; f = 0.f; }
+    if (s >= src - 1) { s = src - 1; f = 0.f; }
+    s0 = s;
+    c0 = aug_round((double)((1.f - f) * 2048.f)); c1 = aug_round((double)(f * 2048.f));      // saturate_cast<short>: both lie in [0, 2048]
+}
+
+// the letterboxed image at (x, y) of its nw x nh extent, three planes
+__device__ __forceinline__ void lb_pixel(const LbImage& im, int x, int y, int px[3]) {
+    const size_t pl = (size_t)im.h * im.w;
+    if (im.nw == im.w && im.nh == im.h) {
+        const size_t o = (size_t)y * im.w + x;
+        px[0] = im.p[o]; px[1] = im.p[pl + o]; px[2] = im.p[2 * pl + o];
+        return;
+    }
+    int sx, a0, a1, sy, b0, b1;
+    lb_resize_coef(x, im.nw, im.w, sx, a0, a1);
+    lb_resize_coef(y, im.nh, im.h, sy, b0, b1);
+    const int sx1 = min(sx + 1, im.w - 1), sy1 = min(sy + 1, im.h - 1);
+    const size_t r0 = (size_t)sy * im.w, r1 = (size_t)sy1 * im.w;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const unsigned char* p = im.p + c * pl;
+        const int S0 = a0 * p[r0 + sx] + a1 * p[r0 + sx1], S1 = a0 * p[r1 + sx] + a1 * p[r1 + sx1];
+        px[c] = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
+    }
+}
+
+// the virtual canvas at (cx, cy): border outside the canvas and inside the letterbox border, the letterboxed image elsewhere
+__device__ __forceinline__ void lb_canvas(const LbImage& im, int cx, int cy, int border, int px[3]) {
+    const int x = cx - im.left, y = cy - im.top;           // outside the canvas implies outside the rectangle: the binding checks that
+    if ((unsigned)x < (unsigned)im.nw && (unsigned)y < (unsigned)im.nh) lb_pixel(im, x, y, px);
+    else px[0] = px[1] = px[2] = border;
+}
+
+__global__ __launch_bounds__(256) void letterbox_kernel(LbArgs a) {
+    const int b = blockIdx.y;
+    const int H = a.H, W = a.W, G = W >> 2;                  // G groups of four pixels per row
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= H * G) return;
+    const long long* t = a.table + (size_t)b * 8;
+    LbImage im;
+    im.p = (const unsigned char*)(uintptr_t)t[0];
+    im.h = (int)t[1]; im.w = (int)t[2]; im.nw = (int)t[3]; im.nh = (int)t[4]; im.left = (int)t[5]; im.top = (int)t[6];
+    const int oy = i / G, ox0 = (i - oy * G) * 4;
+    const int* fl = a.flags + b * 3;
+    const int has_warp = fl[0], ud = fl[1], lr = fl[2];
+    const int y = ud ? H - 1 - oy : oy;                      // position before the flips
+    const double* M = a.minv + (size_t)b * 6;
+    const unsigned char* L = a.lut ? a.lut + (size_t)b * 768 : nullptr;
+    unsigned word[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int ox = ox0 + j;
+        const int x = lr ? W - 1 - ox : ox;
+        int px[3];
+        if (has_warp) {
+            int sx, sy, w[4];
+            aug_warp_taps(M, x, y, sx, sy, w);
+            int acc[3] = {1 << 14, 1 << 14, 1 << 14};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int cy = sy + (k >> 1), cx = sx + (k & 1);
+                int tp[3];
+                if ((unsigned)cx < (unsigned)W && (unsigned)cy < (unsigned)H) lb_canvas(im, cx, cy, a.border, tp);
+                else tp[0] = tp[1] = tp[2] = a.border;
+                acc[0] += w[k] * tp[0]; acc[1] += w[k] * tp[1]; acc[2] += w[k] * tp[2];
+            }
+            px[0] = acc[0] >> 15; px[1] = acc[1] >> 15; px[2] = acc[2] >> 15;
+        } else {
+            lb_canvas(im, x, y, a.border, px);
+        }
+        if (L) aug_hsv_lut(L, px[0], px[1], px[2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) word[c] |= (unsigned)px[c] << (8 * j);
+    }
+    const size_t plane = (size_t)H * W;
+    unsigned char* o = a.dst + (size_t)b * 3 * plane + (size_t)oy * W + ox0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *(unsigned*)(o + c * plane) = word[c];
+}
+
+extern "C" int et_letterbox_u8(const int64_t* table, const double* minv, const uint8_t* lut, const int* flags, uint8_t* out, int B,
+                               int H, int W, int border_value, et_stream_t stream) {
+    if (!table || !minv || !flags || !out) return -1;
+    if (B <= 0 || B > 65535 || H <= 0 || H > 16384 || W <= 0 || W > 16384 || (W & 3) != 0) return -2;
+    if (((uintptr_t)out & 3) != 0) return -3;                   // the 32-bit stores
+    LbArgs a;
+    a.table = (const long long*)table; a.dst = out; a.minv = minv; a.lut = lut; a.flags = flags;
+    a.B = B; a.H = H; a.W = W; a.border = border_value;
+    hipLaunchKernelGGL(letterbox_kernel, dim3(et_cdiv((long long)H * (W >> 2), 256), B), dim3(256), 0, (hipStream_t)stream, a);
+    ET_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- labels of the letterbox batch ---------------------------------------------------------------------------------------------------
+// Per source label (float32), the reference's arithmetic in the reference's dtypes: xywhn2xyxy(ratio_w * w, ratio_h * h, padw, padh)
+// (utils/general.py:640); with has_warp the num_points == 0 label path of random_perspective_keypoints (utils/augmentations.py:176-193,
+// 261-264: corners times M in fp64, min / max, clip x to [0, W] and y to [0, H], box_candidates(box1 = xyxy_f32 * s, area_thr 0.10), the
+// new box assigned back to float32); xyxy2xywhn(w = W, h = H, clip to W - 1e-3 / H - 1e-3) (general.py:649-658); the flips as 1 - v;
+// clip(0, 1) (datasets.py:1027).  geom [B][4] fp64 = {ratio_w * w, ratio_h * h, padw, padh}: padw = dw / 2 can be x.5 and the scalars are
+// doubles in the reference, so the table is fp64 and `wide` [B] says how numpy evaluates y = w * (x - x / 2) + padw on the float32 labels:
+//   0  every scalar is a Python float (img_size an int): weak, the expression is float32 throughout;
+//   1  rect, ratio the Python float 1.0 of min(r, 1.0) but padw a numpy float64 (batch_shapes is a numpy array): float32 product,
+//      float64 sum, rounded to float32 by the assignment;
+//   2  rect, ratio a numpy float64 too: float64 product and sum, rounded to float32 by the assignment.
+// rows [B][2] int32 = {row0, row1}: the image's rows of `labels`; the ranges ascend and do not overlap (the binding checks).  Output and
+// order as et_labeled_mosaic_targets: one workgroup per image scans its keep flags 256 rows at a time and writes survivors to `tmp` at
+// the image's own range, a second launch adds the counts of the images in front and copies.  Without has_warp every row survives.
+struct LbtArgs {
+    const float* labels;        // (L,5)
+    const int* rows;            // [B][2]
+    const double* geom;         // [B][4]
+    const int* wide;            // [B]
+    const double* M;            // [B][9]
+    const double* s;            // [B]
+    const int* flags;           // [B][3] has_warp, flipud, fliplr
+    float* tmp;                 // (L,6)
+    int* counts;                // [B]
+    int B, H, W, L;
+};
+
+__device__ __forceinline__ float lb_xyxy(double scale, float v, double pad, int wide) {
+    if (wide == 2) return (float)(scale * (double)v + pad);
+    const float p = (float)scale * v;
+    return wide ? (float)((double)p + pad) : p + (float)pad;
+}
+
+__global__ __launch_bounds__(256) void letterbox_targets_kernel(LbtArgs a) {
+    __shared__ int wsum[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r0 = max(a.rows[b * 2], 0), r1 = min(a.rows[b * 2 + 1], a.L);
+    const int has_warp = a.flags[b * 3], ud = a.flags[b * 3 + 1], lr = a.flags[b * 3 + 2];
+    const double* g = a.geom + (size_t)b * 4;
+    const int wide = a.wide[b];
+    const float fW = (float)a.W, fH = (float)a.H, hiw = (float)((double)a.W - 1e-3), hih = (float)((double)a.H - 1e-3);
+    int run = 0;
+    for (int base = r0; base < r1; base += 256) {
+        const int row = base + tid;
+        int keep = 0;
+        float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        if (row < r1) {
+            const float* lb = a.labels + (size_t)row * 5;
+            float x1 = lb_xyxy(g[0], lb[1] - lb[3] / 2, g[2], wide), y1 = lb_xyxy(g[1], lb[2] - lb[4] / 2, g[3], wide);
+            float x2 = lb_xyxy(g[0], lb[1] + lb[3] / 2, g[2], wide), y2 = lb_xyxy(g[1], lb[2] + lb[4] / 2, g[3], wide);
+            keep = 1;
+            if (has_warp) {
+                const double* M = a.M + (size_t)b * 9;
+                const double X[4] = {x1, x2, x1, x2}, Y[4] = {y1, y2, y2, y1};
+                double xmin = 0, xmax = 0, ymin = 0, ymax = 0;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const double u = X[c] * M[0] + Y[c] * M[1] + M[2], v = X[c] * M[3] + Y[c] * M[4] + M[5];
+                    xmin = c ? fmin(xmin, u) : u; xmax = c ? fmax(xmax, u) : u;
+                    ymin = c ? fmin(ymin, v) : v; ymax = c ? fmax(ymax, v) : v;
+                }
+                const double dW = (double)a.W, dH = (double)a.H;
+                xmin = fmin(fmax(xmin, 0.0), dW); xmax = fmin(fmax(xmax, 0.0), dW);
+                ymin = fmin(fmax(ymin, 0.0), dH); ymax = fmin(fmax(ymax, 0.0), dH);
+                const float sf = (float)a.s[b];
+                const float w1 = x2 * sf - x1 * sf, h1 = y2 * sf - y1 * sf;
+                const double w2 = xmax - xmin, h2 = ymax - ymin;
+                const double ar = fmax(w2 / (h2 + 1e-16), h2 / (w2 + 1e-16));
+                const float den = w1 * h1 + 1e-16f;
+                keep = (w2 > 2.0) && (h2 > 2.0) && (w2 * h2 / (double)den > 0.1) && (ar < 20.0);
+                x1 = (float)xmin; y1 = (float)ymin; x2 = (float)xmax; y2 = (float)ymax;
+            }
+            const float a0 = fminf(fmaxf(x1, 0.f), hiw), a1 = fminf(fmaxf(y1, 0.f), hih);
+            const float a2 = fminf(fmaxf(x2, 0.f), hiw), a3 = fminf(fmaxf(y2, 0.f), hih);
+            float cx = ((a0 + a2) / 2) / fW, cy = ((a1 + a3) / 2) / fH;
+            const float bw = (a2 - a0) / fW, bh = (a3 - a1) / fH;
+            if (ud) cy = 1 - cy;
+            if (lr) cx = 1 - cx;
+            o[0] = lb[0];
+            o[1] = fminf(fmaxf(cx, 0.f), 1.f); o[2] = fminf(fmaxf(cy, 0.f), 1.f);
+            o[3] = fminf(fmaxf(bw, 0.f), 1.f); o[4] = fminf(fmaxf(bh, 0.f), 1.f);
+        }
+        int inc = keep;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(inc, d);
+            if (lane >= d) inc += up;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int woff = 0;
+        for (int w = 0; w < wave; ++w) woff += wsum[w];
+        const int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (keep) {
+            float* d = a.tmp + (size_t)(r0 + run + woff + inc - 1) * 6;
+            d[0] = (float)b; d[1] = o[0]; d[2] = o[1]; d[3] = o[2]; d[4] = o[3]; d[5] = o[4];
+        }
+        run += tot;
+        __syncthreads();
+    }
+    if (tid == 0) a.counts[b] = run;
+}
+
+__global__ __launch_bounds__(256) void letterbox_targets_compact_kernel(const float* __restrict__ tmp, const int* __restrict__ counts,
+                                                                        const int* __restrict__ rows, float* __restrict__ out,
+                                                                        int* __restrict__ n_out, int B) {
+    __shared__ int wsum[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int part = 0;
+    for (int i = tid; i < b; i += 256) part += counts[i];
+    part = et_wave_sum_i(part);
+    if ((tid & 63) == 0) wsum[tid >> 6] = part;
+    __syncthreads();
+    const int off = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const int cnt = counts[b], r0 = max(rows[b * 2], 0);
+    for (int i = tid; i < cnt * 6; i += 256) out[(size_t)off * 6 + i] = tmp[(size_t)r0 * 6 + i];
+    if (b == B - 1 && tid == 0) *n_out = off + cnt;
+}
+
+extern "C" int et_letterbox_targets(const float* labels, int L_in, const int* rows, const double* geom, const int* wide, const double* M,
+                                    const double* s, const int* flags, int B, int H, int W, float* tmp, int* counts, float* out,
+                                    int* n_out, et_stream_t stream) {
+    if (!labels || !rows || !geom || !wide || !M || !s || !flags || !tmp || !counts || !out || !n_out) return -1;
+    if (B <= 0 || H <= 0 || W <= 0 || L_in <= 0 || L_in > (1 << 28)) return -2;
+    LbtArgs a;
+    a.labels = labels; a.rows = rows; a.geom = geom; a.wide = wide; a.M = M; a.s = s; a.flags = flags; a.tmp = tmp; a.counts = counts;
+    a.B = B; a.H = H; a.W = W; a.L = L_in;
+    hipLaunchKernelGGL(letterbox_targets_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+    ET_CHECK_LAUNCH();
+    hipLaunchKernelGGL(letterbox_targets_compact_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const float*)tmp,
+                       (const int*)counts, rows, out, n_out, B);
+    ET_CHECK_LAUNCH();
+    return 0;
+}

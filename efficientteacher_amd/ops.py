@@ -1421,6 +1421,75 @@ def labeled_mosaic_targets(labels, table, M, scale, flags, s):
     return out, n
 
 
+def letterbox_table(images, geometry, H, W):
+    """the (B, 8) int64 table of et_letterbox_u8 as ONE numpy array: images[b] = the uint8 (3, h, w) device tensor, geometry[b] =
+    (nw, nh, left, top): the reference's new_unpad and the left / top border widths.  Every rectangle is checked against the canvas
+    here (ValueError): the kernel writes the image wherever the table says"""
+    import numpy as np
+    B = len(images)
+    table = np.zeros((B, 8), np.int64)
+    dev = images[0].device
+    for b, (t, geo) in enumerate(zip(images, geometry)):
+        assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[0] == 3 and t.is_contiguous() and t.device == dev
+        nw, nh, left, top = (int(v) for v in geo)
+        table[b, :7] = (t.data_ptr(), t.shape[1], t.shape[2], nw, nh, left, top)
+    if int(W) % 4 != 0 or int(H) <= 0 or int(W) <= 0:
+        raise ValueError(f"letterbox_table: the canvas {H} x {W} needs a positive height and a width that is a multiple of 4")
+    h, w, nw, nh, left, top = (table[:, k] for k in range(1, 7))
+    ok = (h >= 1) & (w >= 1) & (nw >= 1) & (nh >= 1) & (left >= 0) & (top >= 0) & (left + nw <= W) & (top + nh <= H)
+    if not bool(ok.all()):
+        raise ValueError(f"letterbox_table: an empty image or a rectangle outside the {H} x {W} canvas: rows {np.argwhere(~ok).ravel().tolist()}")
+    return table
+
+
+def letterbox_u8(images, geometry, minv, lut, flags, H, W, border_value=114):
+    """A letterbox batch's pixels in one launch (csrc/augment.hip et_letterbox_u8): images / geometry as letterbox_table takes them; minv
+    (B,6) fp64 dst->src maps (read where has_warp), lut (B,3,256) uint8 or None, flags (B,3) int32 (has_warp, flipud, fliplr), all on the
+    device.  -> (B, 3, H, W) uint8 RGB planes"""
+    B = len(images)
+    table = letterbox_table(images, geometry, int(H), int(W))
+    dev = minv.device
+    assert minv.dtype == torch.float64 and minv.shape == (B, 6) and flags.dtype == torch.int32 and flags.shape == (B, 3)
+    assert lut is None or (lut.dtype == torch.uint8 and lut.shape == (B, 3, 256))
+    assert all(t.device == dev for t in images)
+    tdev = torch.from_numpy(table).to(dev, non_blocking=True)
+    out = torch.empty((B, 3, int(H), int(W)), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().et_letterbox_u8(_lib.ptr(tdev), _lib.ptr(minv.contiguous()), _lib.ptr(lut.contiguous()) if lut is not None else None,
+                                           _lib.ptr(flags.contiguous()), _lib.ptr(out), B, int(H), int(W), int(border_value),
+                                           _lib.stream(out)), "et_letterbox_u8")
+    return out
+
+
+def letterbox_targets(labels, rows, geom, wide, M, scale, flags, H, W):
+    """A letterbox batch's targets (csrc/augment.hip et_letterbox_targets).  labels (L_in,5) float32 [cls, x, y, w, h] in image order; rows
+    (B,2) int32 NUMPY array {row0, row1} (checked here, then copied); geom (B,4) fp64 {ratio_w * w, ratio_h * h, padw, padh}, wide (B,)
+    int32 (0 / 1 / 2: see include/et_hip.h), M (B,9) fp64, scale (B,) fp64, flags (B,3) int32 on the device.  -> (out (L_in,6) float32
+    whose first n rows are the reference's collated [img, cls, x, y, w, h], n (1,) int32 on the device)"""
+    import numpy as np
+    L, B = int(labels.shape[0]), int(M.shape[0])
+    dev = M.device
+    assert labels.dtype == torch.float32 and labels.dim() == 2 and labels.shape[1] == 5 and (L == 0 or labels.device == dev)
+    assert isinstance(rows, np.ndarray) and rows.dtype == np.int32 and rows.shape == (B, 2)
+    assert geom.dtype == torch.float64 and geom.shape == (B, 4) and wide.dtype == torch.int32 and wide.shape == (B,)
+    assert M.dtype == torch.float64 and M.shape == (B, 9) and scale.dtype == torch.float64 and scale.shape == (B,)
+    assert flags.dtype == torch.int32 and flags.shape == (B, 3)
+    ok = (rows[:, 0] >= 0).all() and (rows[:, 1] >= rows[:, 0]).all() and (rows[:, 1] <= L).all() and (rows[:-1, 1] <= rows[1:, 0]).all()
+    if not ok:
+        raise ValueError(f"letterbox_targets: the row ranges must ascend, not overlap between images and stay inside the {L} label rows")
+    out = torch.empty((L, 6), dtype=torch.float32, device=dev)
+    n = torch.zeros(1, dtype=torch.int32, device=dev)
+    if L == 0:
+        return out, n
+    tmp = torch.empty((L, 6), dtype=torch.float32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    rdev = torch.from_numpy(np.ascontiguousarray(rows)).to(dev, non_blocking=True)
+    _lib.check(_lib.load().et_letterbox_targets(_lib.ptr(labels.contiguous()), L, _lib.ptr(rdev), _lib.ptr(geom.contiguous()),
+                                                _lib.ptr(wide.contiguous()), _lib.ptr(M.contiguous()), _lib.ptr(scale.contiguous()),
+                                                _lib.ptr(flags.contiguous()), B, int(H), int(W), _lib.ptr(tmp), _lib.ptr(counts),
+                                                _lib.ptr(out), _lib.ptr(n), _lib.stream(out)), "et_letterbox_targets")
+    return out, n
+
+
 def tal_targets_pad(targets, B, img_w, img_h):
     """ComputeTalLoss.preprocess on the device: (n,6) [img, cls, x, y, w, h] normalised -> gt_labels (B,G,1), gt_bboxes (B,G,4) xyxy
     pixels, mask_gt (B,G,1).  G = max(n, 1) without a host synchronisation while n <= 32 * B (the reference loops over

@@ -361,3 +361,211 @@ class LabeledBatchGenerator:
             pending = nxt
         if pending is not None:
             yield pending.result()
+
+
+# ---- the letterbox branch (LoadImagesAndLabels.__getitem__, utils/datasets.py:904-953): val / rect batches and the closed mosaic ----------
+def letterbox_geometry(h, w, new_shape, scaleup):
+    """letterbox(im (h, w), new_shape, auto=False, scaleFill=False, scaleup) without the pixels (utils/augmentations.py:92-123) ->
+    (ratio (rw, rh), (dw, dh), new_unpad (nw, nh), top, left); bottom = new_shape[0] - nh - top and right = new_shape[1] - nw - left
+    (round(d - 0.1) + round(d + 0.1) == 2 d for every d = k / 2).  Written with the reference's own operations so that the TYPES flow as
+    they do there: with an int new_shape everything is a Python number, with a row of rect_batch_shapes (numpy ints) r, dw and dh are
+    numpy float64 -- except the Python 1.0 that min(r, 1.0) returns for r > 1 (LetterboxBatchGenerator reads the label dtype off that)"""
+    if isinstance(new_shape, int):
+        new_shape = (new_shape, new_shape)
+    r = min(new_shape[0] / h, new_shape[1] / w)
+    if not scaleup:
+        r = min(r, 1.0)
+    nw, nh = int(round(w * r)), int(round(h * r))
+    dw, dh = new_shape[1] - nw, new_shape[0] - nh
+    dw /= 2
+    dh /= 2
+    top, left = int(round(dh - 0.1)), int(round(dw - 0.1))
+    return (r, r), (dw, dh), (nw, nh), top, left
+
+
+def rect_batch_shapes(shapes_wh, batch_size, img_size, stride=32, pad=0.0):
+    """Rectangular batches (utils/datasets.py:747-749, 772-795).  shapes_wh: (n, 2) the ORIGINAL (w, h) of every image.  ->
+    (order (n,): the dataset is re-ordered by aspect ratio h / w, position i holds image order[i]; batch_index (n,): the batch of
+    position i; batch_shapes (nb, 2) int: the (H, W) every image of the batch is letterboxed to)"""
+    s = np.array(shapes_wh, dtype=np.float64).reshape(-1, 2)
+    n = s.shape[0]
+    bi = np.floor(np.arange(n) / batch_size).astype(int)
+    nb = bi[-1] + 1
+    ar = s[:, 1] / s[:, 0]
+    irect = ar.argsort()
+    ar = ar[irect]
+    shapes = [[1, 1]] * nb
+    for i in range(nb):
+        ari = ar[bi == i]
+        mini, maxi = ari.min(), ari.max()
+        if maxi < 1:
+            shapes[i] = [maxi, 1]
+        elif mini > 1:
+            shapes[i] = [1, 1 / mini]
+    return irect, bi, np.ceil(np.array(shapes) * img_size / stride + pad).astype(int) * stride
+
+
+class PendingLetterboxBatch(PendingLabeledBatch):
+    """PendingLabeledBatch whose result() carries the letterbox branch's `shapes`"""
+
+    def __init__(self, shapes, *a):
+        super().__init__(*a)
+        self.shapes = shapes
+
+    def result(self):
+        imgs, targets, paths, _ = super().result()
+        return imgs, targets, paths, self.shapes
+
+
+class LetterboxBatchGenerator:
+    """The letterbox branch of the labeled loader on the device, in its two uses: augment=False -- every VALIDATION batch (the reference
+    builds that loader with rect=True, pad=0.5; scaleup = False, no random draw at all) -- and augment=True -- the labeled batches of the
+    CLOSED MOSAIC (the trainer sets dataset.mosaic = False for the last no_aug_epochs; scaleup = True).  The host keeps the recipe --
+    letterbox_geometry, rect_batch_shapes and, for augment, sample()'s draws in the reference's order: the mosaic gate `random.random()`
+    only when self.mosaic is set (`self.mosaic and ...` short-circuits; the default here is the closed mosaic, False),
+    random_perspective_keypoints' eight draws with C and T from the letterboxed H x W, `np.random.uniform(-1, 1, 3)` when an HSV gain is
+    non-zero, the two flip draws -- and two kernels do the work (csrc/augment.hip): et_letterbox_u8 the pixels, et_letterbox_targets the
+    labels.  With rect the dataset is re-ordered as the reference re-orders it: an index is a POSITION of that order and the image
+    behind it is self.order[index]; self.rect_batches lists the positions of every batch.
+    PARITY: geometry, shapes, random streams, matrices, LUTs, flips and labels are pinned on the live reference
+    (tests/golden/letterbox.npz); the 8-bit INTER_LINEAR resize, the warp sampling and the HSV round trip restate OpenCV's published
+    algorithms (no cv2) -- the r == 1 case needs no resize and is a pad, exact by construction.
+    cfg: the reference's config node (cfg.hyp, cfg.Dataset.img_size / np / num_ids); n: the number of images; shapes_wh: their original
+    (w, h), needed with rect.  What the kernels do not cover raises NotImplementedError here."""
+
+    def __init__(self, cfg, n, seed=None, stream=None, augment=False, rect=False, batch_size=None, stride=32, pad=0.0, shapes_wh=None,
+                 image_weights=False, albumentations=False):
+        hyp, ds = cfg.hyp, cfg.Dataset
+        g = lambda node, k, d=0: (node.get(k, d) if hasattr(node, "get") else getattr(node, k, d))
+        if float(g(hyp, "perspective", 0.0)) != 0:
+            raise NotImplementedError("LetterboxBatchGenerator: hyp.perspective != 0 needs cv2.warpPerspective's projective sampling; "
+                                      "the kernel implements the affine warp of every shipped recipe")
+        if int(g(ds, "np", 0)) > 0:
+            raise NotImplementedError("LetterboxBatchGenerator: Dataset.np > 0 (keypoint labels) is not transformed on the device")
+        if int(g(ds, "num_ids", 0)) > 0:
+            raise NotImplementedError("LetterboxBatchGenerator: Dataset.num_ids > 0 (with_id: a tracking id per label) is not carried on the device")
+        if image_weights:
+            raise NotImplementedError("LetterboxBatchGenerator: image_weights re-draws the index list per epoch on the host; not supported")
+        if albumentations:
+            raise NotImplementedError("LetterboxBatchGenerator: the albumentations pipeline runs on host arrays; not supported")
+        self.hyp, self.s, self.n = hyp, int(ds.img_size), int(n)
+        self._g = g
+        self.augment, self.rect = bool(augment), bool(rect)
+        self.mosaic = False                                      # the closed mosaic; True draws the gate and needs hyp.mosaic == 0
+        self.order = np.arange(self.n)
+        if self.rect:
+            if batch_size is None or shapes_wh is None or len(shapes_wh) != self.n:
+                raise ValueError("LetterboxBatchGenerator: rect needs batch_size and the original (w, h) of every image")
+            self.order, self.batch, self.batch_shapes = rect_batch_shapes(shapes_wh, int(batch_size), self.s, stride, pad)
+            self.rect_batches = [np.flatnonzero(self.batch == b).tolist() for b in range(int(self.batch[-1]) + 1)]
+        self.py_rng = random.Random(seed)
+        self.np_rng = np.random.RandomState(seed)
+        self.stream = stream
+
+    def new_shape(self, index):
+        """the final letterboxed shape of position `index` (datasets.py:909): a batch_shapes row (numpy ints) with rect, else img_size"""
+        return self.batch_shapes[self.batch[index]] if self.rect else self.s
+
+    def sample(self, index):
+        """host side of one image: {'shape': (H, W), 'M': (3,3) or None, 's', 'lut': (3,256) u8 or None, 'flipud', 'fliplr'}; without
+        augment nothing is drawn"""
+        hyp, g = self.hyp, self._g
+        shape = self.new_shape(index)
+        H, W = (shape, shape) if isinstance(shape, int) else (int(shape[0]), int(shape[1]))
+        if self.mosaic and self.py_rng.random() < g(hyp, "mosaic", 1.0):
+            raise NotImplementedError("LetterboxBatchGenerator: this image takes the mosaic branch (LabeledBatchGenerator); a batch that "
+                                      "mixes both branches is not supported")
+        if not self.augment:
+            return dict(shape=(H, W), M=None, s=1.0, lut=None, flipud=False, fliplr=False)
+        M, sc = affine_matrix(H, W, g(hyp, "degrees"), g(hyp, "translate"), g(hyp, "scale"), g(hyp, "shear"), self.py_rng)
+        hs = (g(hyp, "hsv_h", 0.0), g(hyp, "hsv_s", 0.0), g(hyp, "hsv_v", 0.0))
+        lut = hsv_luts(*hs, self.np_rng) if any(hs) else None
+        ud = self.py_rng.random() < g(hyp, "flipud", 0.0)
+        lr = self.py_rng.random() < g(hyp, "fliplr", 0.0)
+        return dict(shape=(H, W), M=M, s=sc, lut=lut, flipud=bool(ud), fliplr=bool(lr))
+
+    @staticmethod
+    def label_dtype_mode(scale, pad):
+        """how THIS numpy evaluates xywhn2xyxy's `w * (x - x / 2) + padw` on float32 labels (utils/general.py:640): 0 float32 throughout
+        (Python floats are weak), 1 float32 product and float64 sum, 2 float64 throughout (numpy float64 scalars are not weak)"""
+        x = np.zeros(1, np.float32)
+        p = scale * x
+        return 2 if p.dtype == np.float64 else int((p + pad).dtype == np.float64)
+
+    def launch(self, images, labels, indices, hw0=None, paths=None):
+        """sample every image of the batch and launch the two kernels (on self.stream when given) -> PendingLetterboxBatch"""
+        from .. import ops
+        B = len(indices)
+        samples = [self.sample(int(i)) for i in indices]
+        H, W = samples[0]["shape"]
+        if any(sm["shape"] != (H, W) for sm in samples):
+            raise ValueError("LetterboxBatchGenerator: the images of one batch must share their letterboxed shape (with rect: one of rect_batches)")
+        use_lut = any(sm["lut"] is not None for sm in samples)
+        f64 = np.zeros(B * 20)                                   # one staging array: minv (B,6) | M (B,9) | s (B,) | geom (B,4)
+        minv, M, sc, geom = f64[:B * 6].reshape(B, 6), f64[B * 6:B * 15].reshape(B, 9), f64[B * 15:B * 16], f64[B * 16:].reshape(B, 4)
+        minv[:] = [1, 0, 0, 0, 1, 0]; M[:] = np.eye(3).reshape(9); sc[:] = 1.0
+        i32 = np.zeros(B * 4, np.int32)                          # flags (B,3) | wide (B,)
+        flags, wide = i32[:B * 3].reshape(B, 3), i32[B * 3:]
+        lut = np.tile(np.arange(256, dtype=np.uint8), (B, 3, 1)) if use_lut else None
+        rows = np.zeros((B, 2), np.int32)
+        ims, geo, labs, shapes, row = [], [], [], [], 0
+        for b, (i, sm) in enumerate(zip(indices, samples)):
+            src = int(self.order[int(i)])
+            im = images[src]
+            h, w = int(im.shape[1]), int(im.shape[2])
+            ratio, (dw, dh), (nw, nh), top, left = letterbox_geometry(h, w, self.new_shape(int(i)), scaleup=self.augment)
+            ims.append(im); geo.append((nw, nh, left, top))
+            h0, w0 = (h, w) if hw0 is None else hw0[src]
+            shapes.append(((h0, w0), ((h / h0, w / w0), (dw, dh))))
+            lab = np.asarray(labels[src], dtype=np.float32).reshape(-1, 5)
+            rows[b] = (row, row + lab.shape[0])
+            labs.append(lab); row += lab.shape[0]
+            geom[b] = (ratio[0] * w, ratio[1] * h, dw, dh)
+            wide[b] = self.label_dtype_mode(ratio[0] * w, dw)
+            flags[b] = (self.augment, sm["flipud"], sm["fliplr"])
+            if sm["M"] is not None:
+                minv[b], M[b], sc[b] = invert_affine(sm["M"]), sm["M"].reshape(-1), sm["s"]
+            if sm["lut"] is not None:
+                lut[b] = sm["lut"]
+        lab_all = np.concatenate(labs, 0) if labs else np.zeros((0, 5), np.float32)
+        dev = ims[0].device
+        cuda = dev.type == "cuda"
+        side = self.stream if cuda else None
+        import contextlib
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream(dev))     # the source images were written on the caller's stream
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            t = lambda a: torch.from_numpy(a).to(dev, non_blocking=True)
+            d64, d32 = t(f64), t(i32)
+            dflags = d32[:B * 3].view(B, 3)
+            imgs = ops.letterbox_u8(ims, geo, d64[:B * 6].view(B, 6), t(lut) if use_lut else None, dflags, H, W)
+            out, n_dev = ops.letterbox_targets(t(lab_all), rows, d64[B * 16:].view(B, 4), d32[B * 3:], d64[B * 6:B * 15].view(B, 9),
+                                               d64[B * 15:B * 16], dflags, H, W)
+            n_host = event = None
+            if cuda:
+                n_host = torch.empty(1, dtype=torch.int32).pin_memory()
+                n_host.copy_(n_dev, non_blocking=True)
+                event = torch.cuda.Event()
+                event.record(torch.cuda.current_stream(dev))
+        srcs = [int(self.order[int(i)]) for i in indices]
+        return PendingLetterboxBatch(tuple(shapes), imgs, out, n_dev, n_host, tuple(srcs) if paths is None else tuple(paths[i] for i in srcs),
+                                     event, side)
+
+    def __call__(self, images, labels, indices, hw0=None, paths=None):
+        """images: image -> (3, h, w) uint8 device tensor (what load_image returns, as RGB planes); labels: image -> (n, 5) float32
+        [cls, x, y, w, h] normalised; hw0: image -> (h0, w0) as load_image returns it (None: the images were not resized); indices:
+        the dataset positions of this batch.  -> the reference's batch tuple (imgs (B,3,H,W) uint8, targets (n,6) float32 [img, cls, x, y,
+        w, h], paths, shapes) with shapes[i] = ((h0, w0), ((h / h0, w / w0), (dw, dh))), tensors on the device"""
+        return self.launch(images, labels, indices, hw0, paths).result()
+
+    def batches(self, images, labels, index_batches=None, hw0=None, paths=None):
+        """the dataloader iterable of val.run / Trainer: batch k + 1 is launched before batch k is handed out.  index_batches None:
+        self.rect_batches"""
+        pending = None
+        for idx in (self.rect_batches if index_batches is None else index_batches):
+            nxt = self.launch(images, labels, list(idx), hw0, paths)
+            if pending is not None:
+                yield pending.result()
+            pending = nxt
+        if pending is not None:
+            yield pending.result()

@@ -31,7 +31,7 @@ enum { ET_F32 = 0, ET_BF16 = 1, ET_F16 = 2 };   /* ET_F16 (r05): IEEE half stora
  * for ("gfx950") and the ABI version.  ET_ABI_VERSION changes whenever an entry point is added or a signature / workspace
  * contract changes; a binding must refuse a library whose et_abi_version() differs from the header it was written against
  * (efficientteacher_amd/_lib.py does): a stale libet_hip.so would otherwise read e.g. a new int argument as the stream. */
-#define ET_ABI_VERSION 12
+#define ET_ABI_VERSION 13
 const char* et_build_arch(void);
 int et_abi_version(void);
 
@@ -415,6 +415,33 @@ int et_labeled_mosaic_u8(const int64_t* tiles, const double* minv, const double*
  * no overflow).  tmp (L_in, 6) float32 and counts [B] int32 are scratch.  L_in > 0.                                                   */
 int et_labeled_mosaic_targets(const float* labels, int L_in, const int* table, const double* M, const double* s, const int* flags,
                               int B, int S, float* tmp, int* counts, float* out, int* n_out, et_stream_t stream);
+/* The LETTERBOX branch of the same function (utils/datasets.py:904-953): every validation batch (rect, augment = False) and the labeled
+ * batches of the closed mosaic (no_aug_epochs, augment = True), in one launch.  out (B, 3, H, W) uint8 RGB planes, W % 4 == 0 (else -2),
+ * H != W allowed, 4-byte aligned = flips(augment_hsv(warp(copyMakeBorder(resize(image))))): letterbox (utils/augmentations.py:92-123,
+ * auto = False) and, where has_warp is set, cv2.warpAffine(canvas, M[:2], dsize = (W, H), borderValue) of random_perspective_keypoints
+ * (:125-167) sampled from a VIRTUAL canvas: border_value outside the canvas and in the letterbox border, the letterboxed image inside
+ * [left, left + nw) x [top, top + nh).  Without has_warp the output pixel is the canvas pixel.  The letterboxed image is the source
+ * pixel when (nw, nh) == (w, h) -- a pad, exact by construction -- else cv2.resize(im, (nw, nh), INTER_LINEAR) computed on the fly.
+ * table: DEVICE [B][8] int64 = {device pointer of the (3, h, w) uint8 planes, h, w, nw, nh, left, top, 0}; the caller guarantees
+ * nw, nh >= 1, left, top >= 0, left + nw <= W, top + nh <= H (the Python binding checks it before the launch).  minv [B][6] fp64
+ * dst->src maps (read where has_warp); lut [B][3][256] uint8 or NULL; flags [B][3] int32 (has_warp, flipud, fliplr).
+ * PARITY: the geometry and the recipe are pinned on the reference (tests/golden/letterbox.npz); the 8-bit INTER_LINEAR resize (11-bit
+ * coefficients, OpenCV's resize.cpp), the warp sampling and the HSV round trip RESTATE OpenCV's published algorithms and are
+ * unpinned (no cv2).                                                                                                                   */
+int et_letterbox_u8(const int64_t* table, const double* minv, const uint8_t* lut, const int* flags, uint8_t* out, int B, int H, int W,
+                    int border_value, et_stream_t stream);
+/* The labels of that batch: labels (L_in, 5) float32 [cls, x, y, w, h] normalised, concatenated in image order; rows [B][2] int32
+ * {row0, row1}: rows [row0, row1) belong to image b, ascending and not overlapping; geom [B][4] fp64 {ratio_w * w, ratio_h * h, padw,
+ * padh} (padw = dw / 2 can be x.5: not an int table); wide [B] int32: how numpy evaluates xywhn2xyxy's w * (...) + padw on the float32
+ * labels -- 0 float32 throughout (Python-float scalars), 1 float32 product and fp64 sum, 2 fp64 product and sum (numpy float64 scalars,
+ * which rect's batch_shapes array produces), both rounded to float32 by the assignment; M [B][9] fp64, s [B] fp64 (read where
+ * has_warp), flags as above.  With has_warp: corners times M in fp64, clip x to [0, W] and y to [0, H], box_candidates (area_thr 0.10);
+ * then xyxy2xywhn with its clip to W - 1e-3 / H - 1e-3 in float32, the flips, clip(0, 1).  out (L_in, 6) float32 [img, cls, x, y, w, h]
+ * COMPACTED in collate_fn's order (images ascending, survivors in source order: a stable scan, no atomics); *n_out (device int32) = rows
+ * written (= L_in without has_warp).  tmp (L_in, 6) float32 and counts [B] int32 are scratch.  L_in > 0.                                */
+int et_letterbox_targets(const float* labels, int L_in, const int* rows, const double* geom, const int* wide, const double* M,
+                         const double* s, const int* flags, int B, int H, int W, float* tmp, int* counts, float* out, int* n_out,
+                         et_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Online pseudo labels.  Replaces FairPseudoLabel.create_pseudo_label_online_with_gt
