@@ -136,11 +136,16 @@ def _act_bounds(u, d_u):
     return s, ev_s
 
 
-def _silu_fwd(u, d_u, res, dtype):
+def silu_fwd_error(u, d_u):
+    """(silu(u), d_z0 of section 5): the activation alone -- before the residual, the factor HO and the store"""
     s, ev_s = _act_bounds(u, d_u)
     z0 = u * s
     g = s * (1.0 + u * (1.0 - s))
-    e = u.abs() * (s * ev_s + FLOOR) + R * z0.abs() + g.abs() * d_u + 0.25 * d_u * d_u
+    return z0, u.abs() * (s * ev_s + FLOOR) + R * z0.abs() + g.abs() * d_u + 0.25 * d_u * d_u
+
+
+def _silu_fwd(u, d_u, res, dtype):
+    z0, e = silu_fwd_error(u, d_u)
     z = z0 if res is None else z0 + res
     if res is not None:
         e = e + R * z.abs()
