@@ -13,8 +13,10 @@
 //                    tal_gtmax    one workgroup per (image, gt): max metric / max IoU over the anchors it finally owns
 //                    tal_emit     one thread per (image, anchor): labels, boxes, normalised one-hot scores, fg mask
 //                  Ties: torch.topk leaves the order of EQUAL values unspecified; here the smaller anchor index wins.  Equal
-//                  metrics only occur at exactly 0 (anchor inside the gt whose predicted box misses it), where the pick has
-//                  no effect on the loss (its target score is 0); tests compare on the anchors with a non-zero target.
+//                  metrics are the rule at exactly 0 (anchor inside the gt whose predicted box misses it; every anchor
+//                  outside the box), where the pick has no effect on the loss (its target score is 0), and they DO occur
+//                  above 0: equal scores and a gt centred on a grid corner with equal predicted sizes give bit-equal
+//                  metrics on the mirrored anchors (tests/test_tal_sharp.py pins the smaller-index rule on that case).
 // Compiled with -ffp-contract=off (index decisions depend on fp32 results).
 #include "et_host.h"
 #include <math.h>
